@@ -215,6 +215,36 @@ def test_job_digest_is_split_invariant():
     assert W(0, swapped, iters, succ).sums()[2] != whole[2] or bool((out[10] == out[11]).all())
 
 
+def test_dump_outputs_picks_the_same_frames_for_any_split(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files under 64 MB; a job too large to dump whole is a fixed seeded sample of its frames;
+    the arrays of the shards (zeros outside each shard) add up to the one-shard arrays, which is how N ranks assemble them."""
+    import numpy as np
+    import torch
+    b = _bench()
+    idx = b.dump_frames(4194304, 1280)                                   # the headline job: TM8192, 1280 output bytes per frame
+    assert 0 < len(idx) * 4 * (1280 + 2) <= b.DUMP_BYTES <= 64 * 10 ** 6 - 4096
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < 4194304 and (idx == b.dump_frames(4194304, 1280)).all()
+    assert (b.dump_frames(1000, 1280) == np.arange(1000)).all()
+    monkeypatch.setattr(b, "DUMP_BYTES", 4 * (64 + 2) * 300)             # a 1000-frame job that does not fit: 300 frames sampled
+    sel = b.dump_frames(1000, 64)
+    assert len(sel) == 300
+
+    class W:
+        def __init__(self, first, out, iters, succ):
+            self.first_frame, self.frames, self.out, self.iters, self.succ = first, out.shape[0], out, iters, succ
+    g = torch.Generator().manual_seed(5)
+    out = torch.randint(0, 256, (1000, 64), dtype=torch.uint8, generator=g)
+    iters = torch.randint(0, 26, (1000,), dtype=torch.int32, generator=g)
+    succ = (iters < 25).to(torch.uint8)
+    b.dump_outputs(W(0, out, iters, succ), 1000, 0, 1, str(tmp_path / "whole"))
+    for i, (lo, hi) in enumerate(((0, 333), (333, 334), (334, 1000))):
+        b.dump_outputs(W(lo, out[lo:hi], iters[lo:hi], succ[lo:hi]), 1000, 0, 1, str(tmp_path / f"part{i}"))
+    for name, want in (("output", out), ("iters", iters), ("success", succ)):
+        whole = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert whole.dtype == np.float32 and (whole == want.numpy()[sel]).all()
+        assert (sum(np.load(tmp_path / f"part{i}" / f"{name}.npy") for i in range(3)) == whole).all()
+
+
 def test_whole_job_check_against_the_committed_answers():
     """Round 5's review, next #1: every bench line compares the job's exact results with the committed one-GPU answers."""
     b = _bench()

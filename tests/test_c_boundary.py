@@ -5,9 +5,7 @@ units -- not ctypes with hand-typed argtypes.
 CPU tests: tests/c/example_smoke.c (this repo's C client, shaped like the reference's
 capi/examples/example.c:23-95) compiles for every code with -Wall -Werror, links against the .so,
 and its host-side half runs (static macro sizes == run-time size functions, encoder, LLR helpers);
-the reference's spellings (_TM6140 aliases, one-argument LABRADOR_LDPC_N_() helpers) compile; and,
-where /root/reference exists (this container only), the reference's OWN example.c compiles and
-links against our header and library unchanged.
+and the reference's spellings (_TM6140 aliases, one-argument LABRADOR_LDPC_N_() helpers) compile.
 GPU test: the same client runs end to end (decode_ms_f32 200 iterations, decode_bf) for every code.
 """
 import os
@@ -23,7 +21,6 @@ INC = os.path.join(ROOT, "include")
 SRC = os.path.join(ROOT, "tests", "c", "example_smoke.c")
 NAMES = ["TC128", "TC256", "TC512", "TM1280", "TM1536", "TM2048", "TM5120", "TM6144", "TM8192"]
 CC = shutil.which("cc") or shutil.which("gcc")
-REF_EXAMPLE = "/root/reference/capi/examples/example.c"
 
 pytestmark = pytest.mark.skipif(CC is None, reason="no C compiler")
 
@@ -104,14 +101,6 @@ def test_every_declared_function_links(tmp_path):
     assert r.returncode == 0, r.stderr
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and int(r.stdout) == len(names) >= 30
-
-
-@pytest.mark.skipif(not os.path.exists(REF_EXAMPLE), reason="reference tree not present (GPU box)")
-def test_reference_example_compiles_and_links_unchanged(tmp_path):
-    """The reference's only C client, read where it lies, against OUR include directory and library."""
-    exe = str(tmp_path / "ref_example")
-    r = subprocess.run([CC, "-I" + INC, REF_EXAMPLE, "-o", exe, *link_args()], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
 
 
 BATCH_SRC = os.path.join(ROOT, "tests", "c", "batch_smoke.c")
