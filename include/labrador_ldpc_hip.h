@@ -314,6 +314,39 @@ int labrador_ldpc_decode_ms_batch_f64(enum labrador_ldpc_code code, const double
                                       uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
                                       const struct labrador_ldpc_hip_opts *opts);
 
+/* Soft output: the same decode, returning besides the hard results the decoder's a-posteriori LLR (the marginal) of every variable.
+ *   app     [batch][n + p]        app[f][j] = the reference's va[j] (src/decoder.rs:377, :382-383, :408) when decode_ms returns for
+ *                                 frame f: the marginals of the converging iteration, or of iteration max_iters - 1 on failure;
+ *                                 all zero for max_iters = 0 (:374).  n + p = labrador_ldpc_bf_working_len(code); punctured
+ *                                 variables come last.  The LLR type: integer types saturate as the reference does (i8 reaches
+ *                                 -128); float types equal the reference's values with -0.0 returned as +0.0, and hold a NaN
+ *                                 exactly where the reference's va does -- at the NaN LLRs.
+ *   output, iters, success        exactly as labrador_ldpc_decode_ms_batch_* (per frame, what the hard-only call returns).
+ * Memory modes, device sets, `stream`, argument checks and `variant` as labrador_ldpc_decode_ms_batch_*; with MEM_DEVICE `app` must be
+ * 16-byte aligned (and `output` 8-byte aligned).  Kernels (DESIGN.md "Soft output"):
+ *   - f32, i16, i32: the soft forms of the hard-only call's kernels -- every variant that call accepts;
+ *   - i8: the f32-pipe i8 kernels (those the hard-only call takes for unaligned buffers) whatever the batch size;
+ *     LABRADOR_LDPC_HIP_VARIANT_BITSLICE (64) returns LABRADOR_LDPC_HIP_EUNSUPPORTED: the bit-sliced kernels keep no marginals;
+ *   - f64: the register kernels, except the in-place ones (variant | LABRADOR_LDPC_HIP_VARIANT_PAIR), which keep only the signs of
+ *     most marginals: an explicit in-place variant returns LABRADOR_LDPC_HIP_EUNSUPPORTED, and TM8192, whose tuned f64 kernel is
+ *     in place, runs the workspace kernel (LABRADOR_LDPC_HIP_VARIANT_F64_WORKSPACE) by default.
+ * Returns a status code. */
+int labrador_ldpc_decode_ms_soft_batch_f32(enum labrador_ldpc_code code, const float *llrs, float *app,
+                                           uint8_t *output, uint32_t *iters, uint8_t *success,
+                                           size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_soft_batch_i8 (enum labrador_ldpc_code code, const int8_t *llrs, int8_t *app,
+                                           uint8_t *output, uint32_t *iters, uint8_t *success,
+                                           size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_soft_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, int16_t *app,
+                                           uint8_t *output, uint32_t *iters, uint8_t *success,
+                                           size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_soft_batch_i32(enum labrador_ldpc_code code, const int32_t *llrs, int32_t *app,
+                                           uint8_t *output, uint32_t *iters, uint8_t *success,
+                                           size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_soft_batch_f64(enum labrador_ldpc_code code, const double *llrs, double *app,
+                                           uint8_t *output, uint32_t *iters, uint8_t *success,
+                                           size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --
  * llrs[i], output[i] (8-byte aligned), iters[i], success[i], laid out as in labrador_ldpc_decode_ms_batch_* -- are DEVICE memory

@@ -1,11 +1,12 @@
 // decode_ms_f32.hip -- f32 instantiations of the min-sum kernel (decode_ms::<f32>,
 // /root/reference/src/decoder.rs:69-77, :347-475; C entry capi/src/lib.rs:113-119).
 #include "decode_ms_launch.hpp"
+#include "decode_ms_tables.hpp"
 
 namespace ldpc {
 
 // instantiated in decode_ms_f32_part.hip (three more objects: this one alone took 3 min 40 s of a 4 min build)
-#define LDPC_F32_SIG (const float *, uint8_t *, uint32_t *, uint8_t *, size_t, uint32_t, hipStream_t, unsigned)
+#define LDPC_F32_SIG (const float *, uint8_t *, uint32_t *, uint8_t *, size_t, uint32_t, hipStream_t, unsigned, float *)
 extern template hipError_t launch_pair<TM8192, float> LDPC_F32_SIG;
 extern template hipError_t launch_pair<TM2048, float> LDPC_F32_SIG;
 extern template hipError_t launch_one<TM8192, float, 2> LDPC_F32_SIG;
@@ -14,17 +15,9 @@ extern template hipError_t launch_one<TM5120, float, 1> LDPC_F32_SIG;
 extern template hipError_t launch_one<TM6144, float, 1> LDPC_F32_SIG;
 extern template hipError_t launch_one<TM6144, float, 2> LDPC_F32_SIG;
 
-// code -> default and alternative indices per thread (one table for the dispatch and for decode_ms_reads_llrs_once)
-#define LDPC_TABLE(X) \
-    X(TC128,  float, 1) \
-    X(TC256,  float, 1) \
-    X(TC512,  float, 1) \
-    X(TM1280, float, 1) \
-    X(TM1536, float, 1, 2) \
-    X(TM2048, float, 1, 2) \
-    X(TM5120, float, 1) \
-    X(TM6144, float, 1, 2) \
-    X(TM8192, float, 2, 4)
+// code -> default and alternative indices per thread (decode_ms_tables.hpp: one table for the dispatch, decode_ms_reads_llrs_once
+// and the soft-output dispatch)
+#define LDPC_TABLE LDPC_TABLE_F32
 
 template <>
 hipError_t launch_decode_ms<float>(int code, int variant, const float *llrs, uint8_t *output,

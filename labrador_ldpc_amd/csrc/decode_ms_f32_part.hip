@@ -8,7 +8,7 @@ namespace ldpc {
 #ifndef F32_PART
 #error "compile with -DF32_PART=1, 2 or 3"
 #endif
-#define LDPC_F32_SIG (const float *, uint8_t *, uint32_t *, uint8_t *, size_t, uint32_t, hipStream_t, unsigned)
+#define LDPC_F32_SIG (const float *, uint8_t *, uint32_t *, uint8_t *, size_t, uint32_t, hipStream_t, unsigned, float *)
 
 #if F32_PART == 1
 template hipError_t launch_pair<TM8192, float> LDPC_F32_SIG;          // the metric's kernel, both clamp forms

@@ -1,20 +1,13 @@
 // decode_ms_i16.hip -- i16 instantiations of the min-sum kernel (decode_ms::<i16>,
 // /root/reference/src/decoder.rs:51-59, :347-475; C entry capi/src/lib.rs:105-111).
 #include "decode_ms_launch.hpp"
+#include "decode_ms_tables.hpp"
 
 namespace ldpc {
 
-// code -> default and alternative indices per thread (one table for the dispatch and for decode_ms_reads_llrs_once)
-#define LDPC_TABLE(X) \
-    X(TC128,  int16_t, 1) \
-    X(TC256,  int16_t, 1) \
-    X(TC512,  int16_t, 1) \
-    X(TM1280, int16_t, 1) \
-    X(TM1536, int16_t, 1, 2) \
-    X(TM2048, int16_t, 1) \
-    X(TM5120, int16_t, 1) \
-    X(TM6144, int16_t, 1, 2) \
-    X(TM8192, int16_t, 2)
+// code -> default and alternative indices per thread (decode_ms_tables.hpp: one table for the dispatch, decode_ms_reads_llrs_once
+// and the soft-output dispatch)
+#define LDPC_TABLE LDPC_TABLE_I16
 
 template <>
 hipError_t launch_decode_ms<int16_t>(int code, int variant, const int16_t *llrs, uint8_t *output,

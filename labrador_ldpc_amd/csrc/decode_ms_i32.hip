@@ -2,20 +2,13 @@
 // /root/reference/src/decoder.rs:60-68, :347-475; the Rust generic accepts i32 although the reference's
 // C API does not export it).  Integer arithmetic throughout (Ops<int32_t>, decode_ms_kernel.hpp).
 #include "decode_ms_launch.hpp"
+#include "decode_ms_tables.hpp"
 
 namespace ldpc {
 
-// code -> default and alternative indices per thread (one table for the dispatch and for decode_ms_reads_llrs_once)
-#define LDPC_TABLE(X) \
-    X(TC128,  int32_t, 1) \
-    X(TC256,  int32_t, 1) \
-    X(TC512,  int32_t, 1) \
-    X(TM1280, int32_t, 1) \
-    X(TM1536, int32_t, 1) \
-    X(TM2048, int32_t, 1) \
-    X(TM5120, int32_t, 1) \
-    X(TM6144, int32_t, 1) \
-    X(TM8192, int32_t, 2)
+// code -> default and alternative indices per thread (decode_ms_tables.hpp: one table for the dispatch, decode_ms_reads_llrs_once
+// and the soft-output dispatch)
+#define LDPC_TABLE LDPC_TABLE_I32
 
 template <>
 hipError_t launch_decode_ms<int32_t>(int code, int variant, const int32_t *llrs, uint8_t *output,

@@ -1,20 +1,13 @@
 // decode_ms_i8.hip -- i8 instantiations of the min-sum kernel (decode_ms::<i8>,
 // /root/reference/src/decoder.rs:42-50, :347-475; C entry capi/src/lib.rs:97-103).
 #include "decode_ms_launch.hpp"
+#include "decode_ms_tables.hpp"
 
 namespace ldpc {
 
-// code -> default and alternative indices per thread (one table for the dispatch and for decode_ms_reads_llrs_once)
-#define LDPC_TABLE(X) \
-    X(TC128,  int8_t, 1) \
-    X(TC256,  int8_t, 1) \
-    X(TC512,  int8_t, 1) \
-    X(TM1280, int8_t, 1) \
-    X(TM1536, int8_t, 1, 2) \
-    X(TM2048, int8_t, 1) \
-    X(TM5120, int8_t, 1) \
-    X(TM6144, int8_t, 1, 2) \
-    X(TM8192, int8_t, 2)
+// code -> default and alternative indices per thread (decode_ms_tables.hpp: one table for the dispatch, decode_ms_reads_llrs_once
+// and the soft-output dispatch)
+#define LDPC_TABLE LDPC_TABLE_I8
 
 // The bit-sliced kernel (decode_ms_bs.hip, decode_ms_bitslice.hpp): `variant` 64, and the DEFAULT for the TM codes from
 // bitslice_min_batch() frames up -- one wave (rate 4/5: two) decodes a group of 64 / (M/32) codewords on its own, so it needs a few

@@ -771,10 +771,23 @@ LDPC_DEV int pi_dev(int i, int j)
 template <int CODE, class T, int IPT, int LEAN>
 constexpr bool llr_in_lds() { return (CODE == TC512 || CODE == TC128) && std::is_same_v<T, float> && IPT == 1 && LEAN == 0; }
 
-template <int CODE, class T, int IPT, bool PF, int LEAN, int JW, int FORM, int NANPASS = 0>
+// A marginal as an element of the LLR type: the integer types' registers hold exact integers inside the type's range (IntOps),
+// the others are the type itself.
+template <class T, class R>
+LDPC_DEV T soft_value(R x)
+{
+    if constexpr (std::is_same_v<T, int8_t> || std::is_same_v<T, int16_t>) return (T)(int)x;
+    else return (T)x;
+}
+
+// SOFT: the form with soft output -- every codeword's marginals (decoder.rs:377, the `va` decode_ms returns with) are also stored
+// to `app` ([batch][n + p], the LLR type), one unit-stride store per owned variable in the epilogue (DESIGN.md "Soft output").
+// The hard-only kernels are SOFT = false, where all of it compiles away.
+template <int CODE, class T, int IPT, bool PF, int LEAN, int JW, int FORM, int NANPASS = 0, bool SOFT = false>
 LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                              uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
-                             uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k, char *lds, char *stage)
+                             uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k, char *lds, char *stage,
+                             T *__restrict__ app = nullptr)
 {
     using GEO = Geometry<CODE, T, IPT>;
     using O = Ops<T>;
@@ -800,6 +813,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     // The variable thread overwrites each exchanged u with nv = va - u in the slot it read it from,
     // and publishes the high word (sign) of each exchanged marginal; no array of marginals.
     constexpr bool INPLACE = LEAN == 2;
+    static_assert(!(SOFT && INPLACE), "soft output: the in-place form keeps no marginals of the exchanged columns");
     constexpr int BLK_BYTES = M * SZ;
     constexpr int FLAG_OFF = INPLACE ? NX * BLK_BYTES + NXC * M * 4 : (NX + NXC) * M * SZ;
     auto hi_off = [](int cs) constexpr { return NX * BLK_BYTES + cs * M * 4; };
@@ -1658,6 +1672,40 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
             });
         });
     }
+    // ---- soft output: the marginals themselves (decoder.rs:377), at index C*M + S*NT + t -- lanes run along the index --------
+    // Float types: the kernels read a NaN LLR as +inf (Ops<float>::load / canon_late), the reference's marginal of it is NaN.  Only
+    // a NaN or +inf LLR makes a +inf marginal (every u is finite), so where a wave holds one the LLRs are read again and a NaN put
+    // back -- a wave-uniform branch that ordinary frames never take (no second read of the LLRs, no registers held for it).  A
+    // decode of zero iterations leaves every marginal at the zero of decoder.rs:374.  -0.0 stays +0.0: equal as a value.
+    if constexpr (SOFT) {
+        if (live) {
+            T *const dst = app + (size_t)cw * (NCOLS * M);
+            unsigned tu = (unsigned)t;
+            asm volatile("" : "+v"(tu));        // (as in fetch_llrs: no lane offset hoisted out of the codeword loop into a live VGPR)
+            auto store_app = [&](auto RELOAD_) LDPC_INLINE {
+                static_for<0, IPT>([&](auto S_) LDPC_INLINE {
+                    static_for<0, NCOLS>([&](auto C_) LDPC_INLINE {
+                        constexpr int S = decltype(S_)::value, C = decltype(C_)::value;
+                        const unsigned j = (unsigned)(C * M + S * NT) + tu;
+                        T a = soft_value<T>(va[S][C]);
+                        if constexpr (decltype(RELOAD_)::value != 0 && C < NTX) {
+                            const T x = (llrs + (size_t)cw * N)[j];
+                            a = x != x ? x : a;
+                        }
+                        dst[j] = a;
+                    });
+                });
+            };
+            store_app(IC<0>{});
+            if constexpr (std::is_floating_point_v<T>) {
+                bool inf = false;
+                static_for<0, IPT>([&](auto S_) LDPC_INLINE {
+                    static_for<0, NTX>([&](auto C_) LDPC_INLINE { inf |= va[decltype(S_)::value][decltype(C_)::value] == (R)__builtin_inf(); });
+                });
+                if (__ballot(inf) != 0) store_app(IC<1>{});         // (the same values again, with the NaNs: no else branch to jump over)
+            }
+        }
+    }
     if constexpr (NONAN) {
         static_assert(!NOCAP_POSSIBLE && !NANVOTE && NT >= 64, "first NaN pass: the clamp-vote word is the mark");
         if (maxiters != 0 && __ballot(nan_seen) != 0 && (tid & 63) == 0) cap_flag() = 1;       // (zero iterations: no marginal was ever computed, and none depends on an LLR)
@@ -1725,10 +1773,11 @@ constexpr int min_waves_per_simd()
     return 1;
 }
 
-template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM, int NANPASS>
+template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM, int NANPASS, bool SOFT = false>
 __device__ __forceinline__ void decode_ms_kernel_main(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                                                       uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
-                                                      uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k)
+                                                      uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k,
+                                                      T *__restrict__ app = nullptr)
 {
     using GEO = Geometry<CODE, T, IPT>;
     constexpr int Q = GEO::M / 4;
@@ -1743,17 +1792,17 @@ __device__ __forceinline__ void decode_ms_kernel_main(const T *__restrict__ llrs
     // arrivals of the whole workgroup, whichever copy a wave runs).
     if constexpr (LDPC_QUARTER_SPECIALISE && GEO::G == 1 && GEO::NT == 2 * Q && Q >= 64) {
         if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < Q)
-            decode_ms_body<CODE, T, IPT, PF, LEAN, 0, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage);
+            decode_ms_body<CODE, T, IPT, PF, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
         else
-            decode_ms_body<CODE, T, IPT, PF, LEAN, 1, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage);
+            decode_ms_body<CODE, T, IPT, PF, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
     } else if constexpr (LDPC_QUARTER_SPECIALISE >= 2 && GEO::G == 1 && GEO::NT == 4 * Q && Q >= 64) {
         const int jw = __builtin_amdgcn_readfirstlane((int)threadIdx.x) / Q;
-        if (jw == 0) decode_ms_body<CODE, T, IPT, PF, LEAN, 0, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage);
-        else if (jw == 1) decode_ms_body<CODE, T, IPT, PF, LEAN, 1, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage);
-        else if (jw == 2) decode_ms_body<CODE, T, IPT, PF, LEAN, 2, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage);
-        else decode_ms_body<CODE, T, IPT, PF, LEAN, 3, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage);
+        if (jw == 0) decode_ms_body<CODE, T, IPT, PF, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
+        else if (jw == 1) decode_ms_body<CODE, T, IPT, PF, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
+        else if (jw == 2) decode_ms_body<CODE, T, IPT, PF, LEAN, 2, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
+        else decode_ms_body<CODE, T, IPT, PF, LEAN, 3, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
     } else {
-        decode_ms_body<CODE, T, IPT, PF, LEAN, -1, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage);
+        decode_ms_body<CODE, T, IPT, PF, LEAN, -1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
     }
 }
 
@@ -1780,6 +1829,18 @@ decode_ms_notify_kernel(const T *__restrict__ llrs, uint8_t *__restrict__ output
 {
     decode_ms_kernel_main<CODE, T, IPT, PF, LEAN, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k);
     notify_done(notify, notify_ticket);
+}
+
+// The soft-output form of decode_ms_kernel (SOFT above): the marginals go to `app` as well.  A kernel of its own, so that the
+// hard-only kernels keep their argument list and code.
+template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM = selfcorr_med3<CODE, T>(), int NANPASS = 0>
+__global__ void __launch_bounds__((Geometry<CODE, T, IPT>::WG), (min_waves_per_simd<CODE, T, IPT, LEAN>()))
+soft_decode_ms_kernel(const T *__restrict__ llrs, T *__restrict__ app, uint8_t *__restrict__ output,
+                      uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
+                      uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k)
+{
+    decode_ms_kernel_main<CODE, T, IPT, PF, LEAN, FORM, NANPASS, true>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim,
+                                                                      claim_k, app);
 }
 
 }  // namespace ldpc

@@ -30,6 +30,13 @@ hipError_t launch_decode_ms(int code, int variant, const T *llrs, uint8_t *outpu
 template <class T>
 bool decode_ms_reads_llrs_once(int code, int variant);
 
+// The same decode with soft output: `app` [batch][n + p] receives every codeword's marginals (decoder.rs:377) in the LLR type, and
+// output / iters / success are those of launch_decode_ms<T>.  hipErrorInvalidConfiguration for a `variant` whose kernel has no
+// soft form (decode_ms_soft_*.hip; the header lists them).
+template <class T>
+hipError_t launch_decode_ms_soft(int code, int variant, const T *llrs, T *app, uint8_t *output, uint32_t *iters,
+                                 uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
+
 // Largest |LLR| for which the f32 kernels may drop the FLT_MAX clamp of the exclusive minimum
 // (decoder.rs:414-415) for a run of `maxiters` iterations.  The clamp acts only if a magnitude overflows to
 // infinity.  With L = max |LLR|, V_k = max |v| and U_k = max |u| after iteration k:  U_k <= V_k (an exclusive
@@ -125,7 +132,7 @@ inline uint32_t *claim_counter(hipStream_t stream)
 }
 
 // Resident workgroups per device for one instantiation (occupancy x compute units), cached.
-template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM, int NANPASS = 0>
+template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM, int NANPASS = 0, bool SOFT = false>
 int resident_workgroups()
 {
     using GEO = Geometry<CODE, T, IPT>;
@@ -135,7 +142,10 @@ int resident_workgroups()
     int v = cached[dev].load(std::memory_order_relaxed);
     if (v == 0) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG, 0) != hipSuccess || per_cu < 1)
+        hipError_t e;
+        if constexpr (SOFT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, soft_decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG, 0);
+        if (e != hipSuccess || per_cu < 1)
             per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
         v = per_cu * cus;
@@ -145,9 +155,10 @@ int resident_workgroups()
 }
 
 // Launch one instantiation (IPT indices per thread; LEAN 1 = register-lean check phase, 2 = in-place messages).
-template <int CODE, class T, int IPT, int LEAN, int FORM, int NANPASS = 0>
+// SOFT: the soft-output kernel (soft_decode_ms_kernel), which also writes `app`.
+template <int CODE, class T, int IPT, int LEAN, int FORM, int NANPASS = 0, bool SOFT = false>
 hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
-                           size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
+                           size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags, T *app = nullptr)
 {
     const bool static_stride = (lflags & LF_STATIC) != 0 || NANPASS == 2;     // (the second NaN pass walks its own stride classes)
     using GEO = Geometry<CODE, T, IPT>;
@@ -169,7 +180,7 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
     // the fixed stride: their decodes take tens of microseconds and a workgroup is expensive to start); the fixed stride on
     // the 16x grid for the smaller ones, where the hardware dispatcher is a queue that costs no atomics (the TC codes' draws
     // would hit the device's ceiling of ~85 M same-address atomics per second: claim_chunk()).
-    const size_t resident = (size_t)resident_workgroups<CODE, T, IPT, PF, LEAN, FORM, NANPASS>();
+    const size_t resident = (size_t)resident_workgroups<CODE, T, IPT, PF, LEAN, FORM, NANPASS, SOFT>();
     constexpr bool queue_fed = GEO::WG >= 512;
     uint32_t *claim = (static_stride || maxiters == 0 || !queue_fed) ? nullptr : claim_counter(stream);
     // groups per draw: at least ~8 draws per resident workgroup, so that the last chunks are a small part of a short launch
@@ -185,6 +196,11 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
         grid = resident < (groups + 63) / 64 ? resident : (groups + 63) / 64;
     }
     constexpr bool clamp_form = std::is_same_v<T, float> && FORM == 2;
+    if constexpr (SOFT) {
+        hipLaunchKernelGGL((soft_decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>), dim3((unsigned)grid), dim3(GEO::WG), 0, stream,
+                           llrs, app, output, iters, success, (uint32_t)batch, maxiters, nocap_limit_for(maxiters, clamp_form), claim, (uint32_t)K);
+        return hipGetLastError();
+    } else {
     if constexpr (NANPASS == 0 && notify_kernel_built<CODE>()) {        // (a two-pass decode is two launches: never)
         uint32_t *notify = nullptr, notify_ticket = 0;
         if (take_notify(grid, notify, notify_ticket)) {
@@ -197,6 +213,7 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
     hipLaunchKernelGGL((decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>), dim3((unsigned)grid), dim3(GEO::WG), 0, stream,
                        llrs, output, iters, success, (uint32_t)batch, maxiters, nocap_limit_for(maxiters, clamp_form), claim, (uint32_t)K);
     return hipGetLastError();
+    }
 }
 
 // IPT indices per thread; LEAN 1 = register-lean check phase, 2 = in-place messages.  The f32 kernels with a clamp-free loop
@@ -226,29 +243,29 @@ constexpr bool two_pass_nan()
     return std::is_same_v<T, float> && IPT == 1 && (CODE == TM5120 || CODE == TM1280) && LEAN == 1;
 }
 
-template <int CODE, class T, int IPT, int LEAN>
+template <int CODE, class T, int IPT, int LEAN, bool SOFT = false>
 hipError_t launch_cfg(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
-                      size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
+                      size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags, T *app = nullptr)
 {
     if constexpr (two_pass_nan<CODE, T, IPT, LEAN>()) {
         constexpr int FORM = selfcorr_med3<CODE, T>();
         static_assert(!has_nocap_loop<CODE, T, IPT, LEAN>());
-        bool two = batch >= 2 * (size_t)resident_workgroups<CODE, T, IPT, false, LEAN, FORM, 1>();
+        bool two = batch >= 2 * (size_t)resident_workgroups<CODE, T, IPT, false, LEAN, FORM, 1, SOFT>();
         if (lflags & LF_TWO_PASS) two = true;
         if ((lflags & LF_ONE_PASS) || maxiters == 0 || maxiters == NAN_MARK) two = false;
         if (two) {
-            const hipError_t e = launch_cfg_form<CODE, T, IPT, LEAN, FORM, 1>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+            const hipError_t e = launch_cfg_form<CODE, T, IPT, LEAN, FORM, 1, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
             if (e != hipSuccess) return e;
-            return launch_cfg_form<CODE, T, IPT, LEAN, FORM, 2>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+            return launch_cfg_form<CODE, T, IPT, LEAN, FORM, 2, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
         }
-        return launch_cfg_form<CODE, T, IPT, LEAN, FORM>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+        return launch_cfg_form<CODE, T, IPT, LEAN, FORM, 0, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
     } else
     if constexpr (has_nocap_loop<CODE, T, IPT, LEAN>() && selfcorr_med3<CODE, T>() == 2) {
         if (nocap_limit_for(maxiters, true) >= 8.0f)
-            return launch_cfg_form<CODE, T, IPT, LEAN, 2>(llrs, output, iters, success, batch, maxiters, stream, lflags);
-        return launch_cfg_form<CODE, T, IPT, LEAN, 3>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+            return launch_cfg_form<CODE, T, IPT, LEAN, 2, 0, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
+        return launch_cfg_form<CODE, T, IPT, LEAN, 3, 0, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
     } else {
-        return launch_cfg_form<CODE, T, IPT, LEAN, selfcorr_med3<CODE, T>()>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+        return launch_cfg_form<CODE, T, IPT, LEAN, selfcorr_med3<CODE, T>(), 0, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
     }
 }
 
@@ -280,18 +297,18 @@ constexpr bool kernel_reads_llrs_once()
     return LEAN == 0 || (LEAN == 1 && (std::is_same_v<T, int8_t> || std::is_same_v<T, int16_t>));
 }
 
-template <int CODE, class T, int IPT>
+template <int CODE, class T, int IPT, bool SOFT = false>
 hipError_t launch_one(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
-                      size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
+                      size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags, T *app = nullptr)
 {
-    return launch_cfg<CODE, T, IPT, lean_mode<CODE, T, IPT>()>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+    return launch_cfg<CODE, T, IPT, lean_mode<CODE, T, IPT>(), SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
 }
 
 // Pair-ownership kernel (decode_ms_pair.hpp): one workgroup per CU-resident codeword, persistent.
 constexpr int VARIANT_PAIR = 32;
-template <int CODE, class T, int FORM>
+template <int CODE, class T, int FORM, bool SOFT = false>
 hipError_t launch_pair_form(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
-                            size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
+                            size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags, T *app = nullptr)
 {
     using GEO = PairGeometry<CODE, T>;
     static std::atomic<int> cached[64] = {};
@@ -300,7 +317,10 @@ hipError_t launch_pair_form(const T *llrs, uint8_t *output, uint32_t *iters, uin
     int resident = cached[dev].load(std::memory_order_relaxed);
     if (resident == 0) {
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_pair_kernel<CODE, T, FORM>, GEO::NT, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        hipError_t e;
+        if constexpr (SOFT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, soft_decode_ms_pair_kernel<CODE, T, FORM>, GEO::NT, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_pair_kernel<CODE, T, FORM>, GEO::NT, 0);
+        if (e != hipSuccess || per_cu < 1) per_cu = 1;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
         resident = per_cu * cus;
         cached[dev].store(resident, std::memory_order_relaxed);
@@ -309,14 +329,18 @@ hipError_t launch_pair_form(const T *llrs, uint8_t *output, uint32_t *iters, uin
     size_t grid = (resident <= 256 || claim != nullptr) ? (size_t)resident : (size_t)resident * 16;
     if (grid > batch) grid = batch;
     constexpr bool clamp_form = std::is_same_v<T, float> && FORM == 2;
+    if constexpr (SOFT)
+        hipLaunchKernelGGL((soft_decode_ms_pair_kernel<CODE, T, FORM>), dim3((unsigned)grid), dim3(GEO::NT), 0, stream,
+                           llrs, app, output, iters, success, (uint32_t)batch, maxiters, nocap_limit_for(maxiters, clamp_form), claim);
+    else
     hipLaunchKernelGGL((decode_ms_pair_kernel<CODE, T, FORM>), dim3((unsigned)grid), dim3(GEO::NT), 0, stream,
                        llrs, output, iters, success, (uint32_t)batch, maxiters, nocap_limit_for(maxiters, clamp_form), claim);
     return hipGetLastError();
 }
 
-template <int CODE, class T>
+template <int CODE, class T, bool SOFT = false>
 hipError_t launch_pair(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
-                       size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
+                       size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags, T *app = nullptr)
 {
     if (batch == 0) return hipSuccess;
     if (batch > 0x7FFFFFFFull) return hipErrorInvalidValue;
@@ -325,10 +349,10 @@ hipError_t launch_pair(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t 
         // benchmark's 25 iterations, 2^3 at 28; beyond that real LLRs would fall out of the clamp-free loop altogether, so longer
         // decodes run the v_mul_legacy form (+7 %), whose vote is the clamp-free loop's own
         if (nocap_limit_for(maxiters, true) >= 8.0f)
-            return launch_pair_form<CODE, T, 2>(llrs, output, iters, success, batch, maxiters, stream, lflags);
-        return launch_pair_form<CODE, T, 3>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+            return launch_pair_form<CODE, T, 2, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
+        return launch_pair_form<CODE, T, 3, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
     } else {
-        return launch_pair_form<CODE, T, pair_form_default<T>()>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+        return launch_pair_form<CODE, T, pair_form_default<T>(), SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
     }
 }
 
@@ -344,6 +368,14 @@ hipError_t launch_pair(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t 
 // the same table row as a `case` of decode_ms_reads_llrs_once<T>(): the DEFAULT kernel of the code
 #define LDPC_ONCE_CASE(CODE, T, DEF, ...)                                                        \
     case CODE: return kernel_reads_llrs_once<T, lean_mode<CODE, T, DEF>()>();
+// ... and of launch_decode_ms_soft<T>(): the soft-output forms of the same kernels
+#define LDPC_SOFT_CASE(CODE, T, DEF, ...)                                                        \
+    case CODE: {                                                                                 \
+        constexpr int alts[] = {DEF, ##__VA_ARGS__};                                             \
+        return dispatch_ipt_soft<CODE, T, DEF, ##__VA_ARGS__>(variant == 0 ? alts[0] : variant,  \
+                                                              llrs, app, output, iters, success, \
+                                                              batch, maxiters, stream, lflags);  \
+    }
 #define LDPC_SPLIT_VARIANT()                                                                     \
     unsigned lflags = 0;                                                                         \
     if (variant >= 0) {                                                                          \
@@ -359,6 +391,16 @@ hipError_t dispatch_ipt(int ipt, const T *llrs, uint8_t *output, uint32_t *iters
 {
     hipError_t r = hipErrorInvalidConfiguration;
     (void)((ipt == IPTS ? (r = launch_one<CODE, T, IPTS>(llrs, output, iters, success, batch, maxiters, stream, lflags), true)
+                        : false) || ...);
+    return r;
+}
+
+template <int CODE, class T, int... IPTS>
+hipError_t dispatch_ipt_soft(int ipt, const T *llrs, T *app, uint8_t *output, uint32_t *iters, uint8_t *success,
+                             size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
+{
+    hipError_t r = hipErrorInvalidConfiguration;
+    (void)((ipt == IPTS ? (r = launch_one<CODE, T, IPTS, true>(llrs, output, iters, success, batch, maxiters, stream, lflags, app), true)
                         : false) || ...);
     return r;
 }

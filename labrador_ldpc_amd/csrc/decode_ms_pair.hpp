@@ -57,10 +57,12 @@ constexpr bool all_exchanged_are_pi(const Prototype &p)
 }
 
 // FORM: the self-correction's form (Ops::self_correct): 0 = compare + select, 2 / 3 = the clamp forms
-template <int CODE, class T, int JW, int FORM>
+// SOFT: the soft-output form (decode_ms_body's SOFT): the two adjacent marginals of a thread go to `app` as one store.
+template <int CODE, class T, int JW, int FORM, bool SOFT = false>
 LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                                   uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
-                                  uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, char *lds)
+                                  uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, char *lds,
+                                  T *__restrict__ app = nullptr)
 {
     using GEO = PairGeometry<CODE, T>;
     using O = Ops<T>;
@@ -409,6 +411,25 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                 const unsigned hi = __builtin_bswap32(__builtin_bitreverse32((unsigned)(il >> 32)));
                 w[H] = (unsigned long long)lo | ((unsigned long long)hi << 32);
             });
+            // soft output (decoder.rs:377): marginals 2t and 2t + 1 of the column as one 2 x sizeof(T)-byte store; NaN LLRs put back
+            // as in decode_ms_body -- only a wave holding a +inf marginal of the column reads its LLRs again and stores once more
+            if constexpr (SOFT) {
+                struct alignas(2 * sizeof(T)) Pair { T e, o; };
+                unsigned tu = (unsigned)t;
+                asm volatile("" : "+v"(tu));    // (no lane offset hoisted out of the codeword loop into a live VGPR)
+                Pair *const dst_app = reinterpret_cast<Pair *>(app + (size_t)cw * (NCOLS * M) + C * M + 2 * tu);
+                Pair pr{soft_value<T>(va[0][C]), soft_value<T>(va[1][C])};
+                *dst_app = pr;
+                if constexpr (std::is_floating_point_v<T> && C < NTX) {
+                    if (__ballot(va[0][C] == __builtin_inff() || va[1][C] == __builtin_inff()) != 0) {
+                        const T *src = (llrs + (size_t)cw * N) + (unsigned)(C * M) + 2 * tu;
+                        const T x0 = src[0], x1 = src[1];
+                        pr.e = x0 != x0 ? x0 : pr.e;
+                        pr.o = x1 != x1 ? x1 : pr.o;
+                        *dst_app = pr;
+                    }
+                }
+            }
             if ((t & 63) == 0) {
                 unsigned long long *dst = reinterpret_cast<unsigned long long *>((output + (size_t)cw * GEO::OUT_LEN) + (C * M + 2 * t) / 8);
                 dst[0] = w[0];
@@ -445,6 +466,21 @@ decode_ms_pair_kernel(const T *__restrict__ llrs, uint8_t *__restrict__ output, 
     else if (jw == 1) decode_ms_pair_body<CODE, T, 1, FORM>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, lds);
     else if (jw == 2) decode_ms_pair_body<CODE, T, 2, FORM>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, lds);
     else decode_ms_pair_body<CODE, T, 3, FORM>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, lds);
+}
+
+// The soft-output form of decode_ms_pair_kernel (a kernel of its own: the hard-only one keeps its argument list and code).
+template <int CODE, class T, int FORM = pair_form_default<T>()>
+__global__ void __launch_bounds__((PairGeometry<CODE, T>::NT))
+soft_decode_ms_pair_kernel(const T *__restrict__ llrs, T *__restrict__ app, uint8_t *__restrict__ output, uint32_t *__restrict__ iters_out,
+                           uint8_t *__restrict__ success_out, uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim)
+{
+    using GEO = PairGeometry<CODE, T>;
+    __shared__ __attribute__((aligned(16))) char lds[GEO::LDS_BYTES];
+    const int jw = __builtin_amdgcn_readfirstlane((int)threadIdx.x) / (GEO::M / 8);
+    if (jw == 0) decode_ms_pair_body<CODE, T, 0, FORM, true>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, lds, app);
+    else if (jw == 1) decode_ms_pair_body<CODE, T, 1, FORM, true>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, lds, app);
+    else if (jw == 2) decode_ms_pair_body<CODE, T, 2, FORM, true>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, lds, app);
+    else decode_ms_pair_body<CODE, T, 3, FORM, true>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, lds, app);
 }
 
 }  // namespace ldpc
