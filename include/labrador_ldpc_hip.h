@@ -347,6 +347,27 @@ int labrador_ldpc_decode_ms_soft_batch_f64(enum labrador_ldpc_code code, const d
                                            uint8_t *output, uint32_t *iters, uint8_t *success,
                                            size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
 
+/* Layered schedule (f32 only): block-row layered min-sum decoding instead of the reference's flooding schedule.  Block row r of the
+ * prototype (a "layer": 4 for the TC codes, 3 for the TM codes) updates its checks from marginals that already hold the new messages of
+ * rows 0 .. r-1 of the same sweep; a sweep is one pass over every layer, and the decode stops at the first sweep whose marginals
+ * satisfy every check.  Same arithmetic as decode_ms::<f32> (plain IEEE adds and subtracts, self-correction, min-sum with the FLT_MAX
+ * cap); DESIGN.md 4.5 states the semantics the results are pinned to.  Not the reference's iteration trace: fewer sweeps than its
+ * iterations, and a lower frame error rate at the same cap.
+ *   output      hard decisions of the returned sweep's marginals, as labrador_ldpc_decode_ms_batch_f32;
+ *   iters       the 0-based index of the succeeding sweep, or max_iters on failure (0 for max_iters = 0);
+ *   success     1 when every check is satisfied;
+ *   app         (soft form) the marginals of the returned sweep, [batch][n + p]: -0.0 returned as +0.0, NaN exactly at NaN LLRs;
+ *               all zero for max_iters = 0.
+ * A NaN LLR gives the hard results of a +inf LLR.  Arguments, memory modes, device sets, `stream` and alignment rules as
+ * labrador_ldpc_decode_ms_batch_f32 / labrador_ldpc_decode_ms_soft_batch_f32.  `variant` 0 is the only kernel; any other value returns
+ * LABRADOR_LDPC_HIP_EUNSUPPORTED.  Returns a status code. */
+int labrador_ldpc_decode_ms_layered_batch_f32(enum labrador_ldpc_code code, const float *llrs, uint8_t *output,
+                                              uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                              const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_soft_batch_f32(enum labrador_ldpc_code code, const float *llrs, float *app,
+                                                   uint8_t *output, uint32_t *iters, uint8_t *success,
+                                                   size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --
  * llrs[i], output[i] (8-byte aligned), iters[i], success[i], laid out as in labrador_ldpc_decode_ms_batch_* -- are DEVICE memory

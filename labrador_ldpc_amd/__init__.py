@@ -79,6 +79,8 @@ SYMBOLS = {
     "labrador_ldpc_decode_ms_batch_i32": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_decode_ms_batch_f64": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     **{f"labrador_ldpc_decode_ms_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f32", "i8", "i16", "i32", "f64")},
+    "labrador_ldpc_decode_ms_layered_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
+    "labrador_ldpc_decode_ms_layered_soft_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -361,13 +363,26 @@ class LDPCCode(enum.IntEnum):
         torch CUDA tensors are device-resident buffers: the call only enqueues the
         kernel on the tensor's device, on `stream` (default: torch's current stream).
         Returns (output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8)."""
+        return self._batch_call("labrador_ldpc_decode_ms_batch_", llrs, maxiters, output, iters, success, variant, stream, devices)
+
+    def decode_ms_layered_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
+                                variant: int = 0, stream: Optional[int] = None, devices=None):
+        """decode_ms_batch with the block-row LAYERED schedule instead of the reference's flooding one (f32 LLRs only;
+        labrador_ldpc_decode_ms_layered_batch_f32): each block row updates its checks from marginals that already
+        hold the new messages of the rows before it, so a decode takes fewer sweeps and fails less often at the same cap.
+        `iters` counts sweeps (0-based index of the succeeding one, maxiters on failure).  Buffers, `stream` and `devices` as
+        decode_ms_batch; `variant` 0 is the only kernel.  Returns (output, iters, success)."""
+        return self._batch_call("labrador_ldpc_decode_ms_layered_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices)
+
+    def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices):
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
         if llrs.ndim != 2 or llrs.shape[1] != self.n():
             raise ValueError("llrs must be [batch, n]")
         batch = llrs.shape[0]
         try:
-            fn = getattr(lib, "labrador_ldpc_decode_ms_batch_" + _suffix(llrs), None)
+            fn = getattr(lib, prefix + _suffix(llrs), None)
         except KeyError:
             fn = None
         if fn is None:
@@ -416,13 +431,24 @@ class LDPCCode(enum.IntEnum):
         Buffers and `devices` / `stream` as in decode_ms_batch.  Returns (app[batch, n + p] in the dtype of `llrs` -- punctured
         variables last --, output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8); output, iters and success are
         what decode_ms_batch returns."""
+        return self._soft_batch_call("labrador_ldpc_decode_ms_soft_batch_", llrs, maxiters, app, output, iters, success, variant, stream,
+                                     devices)
+
+    def decode_ms_layered_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
+                                     variant: int = 0, stream: Optional[int] = None, devices=None):
+        """decode_ms_layered_batch with soft output (labrador_ldpc_decode_ms_layered_soft_batch_f32): also the marginals of the
+        returned sweep.  Buffers and return shapes as decode_ms_soft_batch: (app[batch, n + p], output, iters, success)."""
+        return self._soft_batch_call("labrador_ldpc_decode_ms_layered_soft_batch_", llrs, maxiters, app, output, iters, success, variant,
+                                     stream, devices)
+
+    def _soft_batch_call(self, prefix, llrs, maxiters, app, output, iters, success, variant, stream, devices):
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
         if llrs.ndim != 2 or llrs.shape[1] != self.n():
             raise ValueError("llrs must be [batch, n]")
         batch, np_len = llrs.shape[0], self.n() + self.punctured_bits()
         try:
-            fn = getattr(lib, "labrador_ldpc_decode_ms_soft_batch_" + _suffix(llrs), None)
+            fn = getattr(lib, prefix + _suffix(llrs), None)
         except KeyError:
             fn = None
         if fn is None:

@@ -5,7 +5,9 @@ encode -> hard_to_llrs (+-1) -> add Normal(0, sigma) noise -> decode_ms (100 ite
 errors in the first k bits, until trials*k > 5e7 or errors > 5000 (:50); one CSV line per SNR (:62):
     code,snr,trials,bits,errors,ber
 Here a trial batch runs entirely on the device: labrador_ldpc_encode_batch -> labrador_ldpc_hip_awgn_f32
--> labrador_ldpc_decode_ms_batch_f32, errors counted with torch bit ops (plumbing).
+-> labrador_ldpc_decode_ms_batch_f32, errors counted with torch bit ops (plumbing).  `--schedule layered` decodes with
+labrador_ldpc_decode_ms_layered_batch_f32 instead (block-row layered schedule), so both FER curves can be drawn
+from the same frames; the default, flooding, is the reference's decoder and keeps the output unchanged.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -28,8 +30,11 @@ def sigma_for(code, snr_db: float, noise: str) -> float:
 
 
 def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100, batch: int = 65536,
-              max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0):
-    """One SNR point.  Returns (trials, bits, errors, ber, frame_errors)."""
+              max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding"):
+    """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
+    reference's decoder) or "layered" (decode_ms_layered_batch)."""
+    if schedule not in ("flooding", "layered"):
+        raise ValueError(f"unknown schedule {schedule!r}")
     import torch
     dev = torch.device("cuda", device)
     k8 = code.k() // 8
@@ -43,7 +48,10 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         data = torch.randint(0, 256, (batch, k8), dtype=torch.uint8, device=dev, generator=g)
         cw = code.encode_batch(data)                                         # perftest/src/main.rs:10-12
         llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
-        out, _, _ = code.decode_ms_batch(llrs, maxiters)                    # :22
+        if schedule == "layered":
+            out, _, _ = code.decode_ms_layered_batch(llrs, maxiters)
+        else:
+            out, _, _ = code.decode_ms_batch(llrs, maxiters)                # :22
         diff = out[:, :k8] ^ data                                            # :23-28
         per_frame = popcnt[diff.long()].sum(dim=1)
         errors += int(per_frame.sum())
@@ -65,11 +73,12 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--max-bits", type=float, default=5e7)
     ap.add_argument("--max-errors", type=int, default=5000)
+    ap.add_argument("--schedule", choices=["flooding", "layered"], default="flooding")
     args = ap.parse_args(argv)
     code = LDPCCode[args.code]
     for snr in (float(x) for x in args.snrs.split(",")):
         trials, bits, errors, ber, fe = ms_trials(code, snr, args.noise, args.maxiters, args.batch,
-                                                  args.max_bits, args.max_errors)
+                                                  args.max_bits, args.max_errors, schedule=args.schedule)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 
