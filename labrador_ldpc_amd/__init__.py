@@ -375,73 +375,8 @@ class LDPCCode(enum.IntEnum):
         return self._batch_call("labrador_ldpc_decode_ms_layered_batch_", llrs, maxiters, output, iters, success, variant, stream,
                                 devices)
 
-    def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices):
-        if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
-            raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
-        if llrs.ndim != 2 or llrs.shape[1] != self.n():
-            raise ValueError("llrs must be [batch, n]")
-        batch = llrs.shape[0]
-        try:
-            fn = getattr(lib, prefix + _suffix(llrs), None)
-        except KeyError:
-            fn = None
-        if fn is None:
-            raise LdpcHipError(f"no batched kernel for dtype {llrs.dtype}")
-        keep = None
-        if _is_torch(llrs):
-            import torch
-            if not llrs.is_cuda:
-                raise ValueError("torch tensors must live on the GPU (use numpy for host buffers)")
-            if not llrs.is_contiguous():
-                raise ValueError("llrs must be contiguous")
-            if devices is not None:
-                raise ValueError("device-resident buffers live on one device; `devices` is for host buffers")
-            dev = llrs.device
-            if output is None:
-                output = torch.empty((batch, self.output_len()), dtype=torch.uint8, device=dev)
-            if iters is None:
-                iters = torch.empty((batch,), dtype=torch.int32, device=dev)
-            if success is None:
-                success = torch.empty((batch,), dtype=torch.uint8, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, variant, 0, None)
-        else:
-            llrs = np.ascontiguousarray(llrs)
-            if output is None:
-                output = np.empty((batch, self.output_len()), dtype=np.uint8)
-            if iters is None:
-                iters = np.empty((batch,), dtype=np.uint32)
-            if success is None:
-                success = np.empty((batch,), dtype=np.uint8)
-            opts, keep = _host_opts(stream, variant, devices)
-        _check_result_buffer(output, llrs, (batch, self.output_len()), "u8", "output")
-        _check_result_buffer(iters, llrs, (batch,), "i32", "iters")
-        _check_result_buffer(success, llrs, (batch,), "u8", "success")
-        _check(fn(int(self), _ptr(llrs), _ptr(output), _ptr(iters), _ptr(success), batch, maxiters,
-                  ctypes.byref(opts)))
-        del keep
-        return output, iters, success
-
-    def decode_ms_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
-                             variant: int = 0, stream: Optional[int] = None, devices=None):
-        """decode_ms_batch with soft output: also the decoder's a-posteriori LLR of every variable, the reference's `va`
-        (src/decoder.rs:377) when decode_ms returns (labrador_ldpc_decode_ms_soft_batch_*).
-
-        Buffers and `devices` / `stream` as in decode_ms_batch.  Returns (app[batch, n + p] in the dtype of `llrs` -- punctured
-        variables last --, output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8); output, iters and success are
-        what decode_ms_batch returns."""
-        return self._soft_batch_call("labrador_ldpc_decode_ms_soft_batch_", llrs, maxiters, app, output, iters, success, variant, stream,
-                                     devices)
-
-    def decode_ms_layered_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
-                                     variant: int = 0, stream: Optional[int] = None, devices=None):
-        """decode_ms_layered_batch with soft output (labrador_ldpc_decode_ms_layered_soft_batch_f32): also the marginals of the
-        returned sweep.  Buffers and return shapes as decode_ms_soft_batch: (app[batch, n + p], output, iters, success)."""
-        return self._soft_batch_call("labrador_ldpc_decode_ms_layered_soft_batch_", llrs, maxiters, app, output, iters, success, variant,
-                                     stream, devices)
-
-    def _soft_batch_call(self, prefix, llrs, maxiters, app, output, iters, success, variant, stream, devices):
+    def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None):
+        # soft: the call also writes the marginals to `app` [batch, n + p] in the dtype of `llrs`, which comes back first
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
         if llrs.ndim != 2 or llrs.shape[1] != self.n():
@@ -463,7 +398,7 @@ class LDPCCode(enum.IntEnum):
             if devices is not None:
                 raise ValueError("device-resident buffers live on one device; `devices` is for host buffers")
             dev = llrs.device
-            if app is None:
+            if soft and app is None:
                 app = torch.empty((batch, np_len), dtype=llrs.dtype, device=dev)
             if output is None:
                 output = torch.empty((batch, self.output_len()), dtype=torch.uint8, device=dev)
@@ -473,13 +408,13 @@ class LDPCCode(enum.IntEnum):
                 success = torch.empty((batch,), dtype=torch.uint8, device=dev)
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
-            if not _is_torch(app) or app.device != dev or app.dtype != llrs.dtype or tuple(app.shape) != (batch, np_len) \
-                    or not app.is_contiguous():
+            if soft and (not _is_torch(app) or app.device != dev or app.dtype != llrs.dtype or tuple(app.shape) != (batch, np_len)
+                         or not app.is_contiguous()):
                 raise ValueError(f"app must be a contiguous {llrs.dtype} tensor of shape {(batch, np_len)} on {dev}")
             opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, variant, 0, None)
         else:
             llrs = np.ascontiguousarray(llrs)
-            if app is None:
+            if soft and app is None:
                 app = np.empty((batch, np_len), dtype=llrs.dtype)
             if output is None:
                 output = np.empty((batch, self.output_len()), dtype=np.uint8)
@@ -487,17 +422,35 @@ class LDPCCode(enum.IntEnum):
                 iters = np.empty((batch,), dtype=np.uint32)
             if success is None:
                 success = np.empty((batch,), dtype=np.uint8)
-            if not isinstance(app, np.ndarray) or app.dtype != llrs.dtype or app.shape != (batch, np_len) \
-                    or not app.flags.c_contiguous or not app.flags.writeable:
+            if soft and (not isinstance(app, np.ndarray) or app.dtype != llrs.dtype or app.shape != (batch, np_len)
+                         or not app.flags.c_contiguous or not app.flags.writeable):
                 raise ValueError(f"app must be a writable C-contiguous {llrs.dtype} array of shape {(batch, np_len)}")
             opts, keep = _host_opts(stream, variant, devices)
         _check_result_buffer(output, llrs, (batch, self.output_len()), "u8", "output")
         _check_result_buffer(iters, llrs, (batch,), "i32", "iters")
         _check_result_buffer(success, llrs, (batch,), "u8", "success")
-        _check(fn(int(self), _ptr(llrs), _ptr(app), _ptr(output), _ptr(iters), _ptr(success), batch, maxiters,
-                  ctypes.byref(opts)))
+        results = (app, output, iters, success) if soft else (output, iters, success)
+        _check(fn(int(self), _ptr(llrs), *(_ptr(r) for r in results), batch, maxiters, ctypes.byref(opts)))
         del keep
-        return app, output, iters, success
+        return results
+
+    def decode_ms_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
+                             variant: int = 0, stream: Optional[int] = None, devices=None):
+        """decode_ms_batch with soft output: also the decoder's a-posteriori LLR of every variable, the reference's `va`
+        (src/decoder.rs:377) when decode_ms returns (labrador_ldpc_decode_ms_soft_batch_*).
+
+        Buffers and `devices` / `stream` as in decode_ms_batch.  Returns (app[batch, n + p] in the dtype of `llrs` -- punctured
+        variables last --, output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8); output, iters and success are
+        what decode_ms_batch returns."""
+        return self._batch_call("labrador_ldpc_decode_ms_soft_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
+                                soft=True, app=app)
+
+    def decode_ms_layered_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
+                                     variant: int = 0, stream: Optional[int] = None, devices=None):
+        """decode_ms_layered_batch with soft output (labrador_ldpc_decode_ms_layered_soft_batch_f32): also the marginals of the
+        returned sweep.  Buffers and return shapes as decode_ms_soft_batch: (app[batch, n + p], output, iters, success)."""
+        return self._batch_call("labrador_ldpc_decode_ms_layered_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices, soft=True, app=app)
 
     def decode_ms_batch_multi(self, parts, maxiters: int = 50, variant: int = 0):
         """Decode several device-resident batches -- one torch CUDA tensor `llrs[frames_i, n]` per part, each on its own (or the

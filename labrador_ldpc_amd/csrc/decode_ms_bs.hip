@@ -13,7 +13,6 @@
 // worth +2 % on the two-wave kernels and +0.5 % on rate 2/3 but costs the rate-1/2 kernels (168 registers, spilling) 2.5 %
 // (profiles/r05_kbench/permute_pipeline.txt, section 7).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 
 #ifndef BS_TU
@@ -23,6 +22,7 @@
 #include "decode_ms_bitslice.hpp"
 #include "decode_ms_bitslice_split.hpp"
 #include "hip_backend.hpp"
+#include "occupancy.hpp"
 
 namespace ldpc {
 namespace bs {
@@ -147,17 +147,7 @@ hipError_t launch_split_refill(const int8_t *llrs, uint8_t *output, uint32_t *it
     constexpr int G = Geo<CODE>::G;
     if (batch == 0) return hipSuccess;
     if (batch > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int resident = cached[dev].load(std::memory_order_relaxed);
-    if (resident == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_bs_split_refill_kernel<CODE>, 128, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = per_cu * cus;
-        cached[dev].store(resident, std::memory_order_relaxed);
-    }
+    const int resident = resident_workgroups<decode_ms_bs_split_refill_kernel<CODE>, 128>();
     // frames per draw: four rounds of slots, fewer for short launches (at least ~4 draws per resident workgroup)
     size_t chunk = 4 * (size_t)G;
     while (chunk > (size_t)G && batch / chunk < 4 * (size_t)resident) chunk /= 2;
@@ -190,17 +180,7 @@ hipError_t launch_refill(const int8_t *llrs, uint8_t *output, uint32_t *iters, u
     constexpr int G = Geo<CODE>::G;
     if (batch == 0) return hipSuccess;
     if (batch > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int resident = cached[dev].load(std::memory_order_relaxed);
-    if (resident == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_bs_refill_kernel<CODE>, 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = per_cu * cus;
-        cached[dev].store(resident, std::memory_order_relaxed);
-    }
+    const int resident = resident_workgroups<decode_ms_bs_refill_kernel<CODE>, 64>();
     // frames per draw: 8 rounds of slots, fewer for short launches (at least ~4 draws per resident wave)
     size_t chunk = 8 * (size_t)G;
     while (chunk > (size_t)G && batch / chunk < 4 * (size_t)resident) chunk /= 2;

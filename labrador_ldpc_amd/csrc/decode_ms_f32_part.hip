@@ -1,5 +1,6 @@
 // decode_ms_f32_part.hip -- the heavy f32 instantiations of the min-sum kernel, compiled as three objects of their own
-// (Makefile: -DF32_PART=1/2/3) so that the build stays parallel: decode_ms_f32.hip declares them `extern template`.
+// (Makefile: -DF32_PART=1/2/3, and with -DLDPC_SOFT=1 three more for the soft-output forms) so that the build stays parallel:
+// decode_ms_f32.hip declares them `extern template`.
 // (decode_ms::<f32>, /root/reference/src/decoder.rs:69-77, :347-475)
 #include "decode_ms_launch.hpp"
 
@@ -8,18 +9,10 @@ namespace ldpc {
 #ifndef F32_PART
 #error "compile with -DF32_PART=1, 2 or 3"
 #endif
-#define LDPC_F32_SIG (const float *, uint8_t *, uint32_t *, uint8_t *, size_t, uint32_t, hipStream_t, unsigned, float *)
+#define F32_CAT2(a, b) a##b
+#define F32_CAT(a, b) F32_CAT2(a, b)
+#define LDPC_F32_INSTANTIATE(...) template hipError_t __VA_ARGS__ LDPC_F32_SIG;
 
-#if F32_PART == 1
-template hipError_t launch_pair<TM8192, float> LDPC_F32_SIG;          // the metric's kernel, both clamp forms
-#elif F32_PART == 2
-template hipError_t launch_pair<TM2048, float> LDPC_F32_SIG;
-template hipError_t launch_one<TM8192, float, 2> LDPC_F32_SIG;
-template hipError_t launch_one<TM8192, float, 4> LDPC_F32_SIG;
-#else
-template hipError_t launch_one<TM5120, float, 1> LDPC_F32_SIG;        // one-pass kernel and the two NaN passes (two_pass_nan())
-template hipError_t launch_one<TM6144, float, 1> LDPC_F32_SIG;
-template hipError_t launch_one<TM6144, float, 2> LDPC_F32_SIG;
-#endif
+F32_CAT(LDPC_F32_PART_, F32_PART)(LDPC_F32_INSTANTIATE, LDPC_SOFT)
 
 }  // namespace ldpc

@@ -16,15 +16,9 @@
 //   check phase     thread i of block row r:     decoder.rs:419-447 for its edges in order, then
 //                   decoder.rs:391-405 (next u) from the row's (min1, min2, sign)
 // Results equal the reference's bit for bit (IEEE f64 add/sub, no contraction).
-#include "decode_ms_f64_ws.hpp"
-#include "decode_ms_tables.hpp"
+#include "decode_ms_f64_ws.hpp"        // the workspace kernel and the f64 dispatch
 
 namespace ldpc {
-
-hipError_t launch_decode_ms_f64_reg(int code, int ipt, int lean, const double *llrs, uint8_t *output, uint32_t *iters,
-                                    uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
-
-// the tuned default per code: F64_TUNED (decode_ms_tables.hpp)
 
 // only the plain register kernel holds its f64 LLRs in registers (kernel_reads_llrs_once)
 template <>
@@ -32,33 +26,6 @@ bool decode_ms_reads_llrs_once<double>(int code, int variant)
 {
     if (variant != 0 || !valid_code(code)) return false;
     return (F64_TUNED[code] & (16 | 32)) == 0;
-}
-
-// variant: 0 = tuned default; 100 = the workspace kernel above; otherwise the register kernel with
-// IPT = variant & 15, the register-lean check phase if variant & 16, in-place messages if variant & 32.
-template <>
-hipError_t launch_decode_ms<double>(int code, int variant, const double *llrs, uint8_t *output, uint32_t *iters,
-                                    uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
-{
-    if (batch == 0) return hipSuccess;
-    if (!valid_code(code)) return hipErrorInvalidValue;
-    if (variant >= 0) variant &= ~VARIANT_FLAGS;           // (the f64 kernels always draw from the launch's queue)
-    if (variant == 0) variant = F64_TUNED[code];
-    if (variant != 100)
-        return launch_decode_ms_f64_reg(code, variant & 15, (variant & 32) ? 2 : ((variant & 16) ? 1 : 0), llrs, output, iters, success, batch,
-                                        maxiters, stream);
-    switch (code) {
-        case TC128:  return launch_f64<TC128>(llrs, output, iters, success, batch, maxiters, stream);
-        case TC256:  return launch_f64<TC256>(llrs, output, iters, success, batch, maxiters, stream);
-        case TC512:  return launch_f64<TC512>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM1280: return launch_f64<TM1280>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM1536: return launch_f64<TM1536>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM2048: return launch_f64<TM2048>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM5120: return launch_f64<TM5120>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM6144: return launch_f64<TM6144>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM8192: return launch_f64<TM8192, 1024, 256>(llrs, output, iters, success, batch, maxiters, stream);   // 0.122 vs 0.081 M/s at 256 threads x 1024 workgroups
-        default: return hipErrorInvalidValue;
-    }
 }
 
 }  // namespace ldpc

@@ -1,5 +1,6 @@
-// decode_ms_f64_ws.hpp -- the f64 workspace kernel (`variant` 100) and its launcher, shared by decode_ms_f64.hip (hard-only) and
-// decode_ms_soft_f64.hip (LDPC_F64_WS_SOFT: the soft-output form).  The description is at the top of decode_ms_f64.hip.
+// decode_ms_f64_ws.hpp -- the f64 workspace kernel (`variant` 100), its launcher and the f64 dispatch, included once per form: by
+// decode_ms_f64.hip (hard-only) and by object 0 of decode_ms_f64_reg.hip's soft-output build (LDPC_SOFT=1).  The description is at
+// the top of decode_ms_f64.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,12 +26,12 @@ LDPC_DEV int pi_inv_dev(int x)
     return (j << LQ) + ((x - phi) & (Q - 1));
 }
 
-// LDPC_F64_WS_SOFT (defined by decode_ms_soft_f64.hip before including this header): the kernel is the soft-output form,
+// LDPC_SOFT=1: the kernel is the soft-output form,
 // soft_decode_ms_f64_kernel, which also stores the marginals (decoder.rs:377) -- this kernel keeps them in LDS exactly as the
 // reference computes them, -0.0 and NaN included -- to app[batch][n + p].  Without it, the hard-only kernel, unchanged.
 template <int CODE, int F64_THREADS>
 __global__ void __launch_bounds__(F64_THREADS)
-#ifndef LDPC_F64_WS_SOFT
+#if !LDPC_SOFT
 decode_ms_f64_kernel(const double *__restrict__ llrs, uint8_t *__restrict__ output,
                      uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                      double *__restrict__ workspace, uint32_t batch, uint32_t maxiters)
@@ -143,7 +144,7 @@ soft_decode_ms_f64_kernel(const double *__restrict__ llrs, double *__restrict__ 
             for (int q = 0; q < 8; ++q) b |= (uint32_t)(va[8 * j + q] < 0.0) << (7 - q);
             output[(size_t)cw * (NP / 8) + j] = (uint8_t)b;
         }
-#ifdef LDPC_F64_WS_SOFT
+#if LDPC_SOFT
         for (int x = tid; x < NP; x += F64_THREADS) app[(size_t)cw * NP + x] = va[x];
 #endif
         if (tid == 0) { iters_out[cw] = iters; success_out[cw] = ok ? 1 : 0; }
@@ -152,20 +153,15 @@ soft_decode_ms_f64_kernel(const double *__restrict__ llrs, double *__restrict__ 
 }
 
 template <int CODE, int F64_THREADS = 256, int GRID = 1024>
-#ifndef LDPC_F64_WS_SOFT
-hipError_t launch_f64(const double *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
+hipError_t launch_f64(const double *llrs, double *app, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                       uint32_t maxiters, hipStream_t stream)
-#else
-hipError_t launch_f64(const double *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
-                      uint32_t maxiters, hipStream_t stream, double *app)
-#endif
 {
     constexpr size_t E = (size_t)CODES[CODE].proto->n_blocks * CODES[CODE].m;
     const unsigned grid = (unsigned)(batch < GRID ? batch : GRID);
     double *ws = nullptr;
     hipError_t e = hipMallocAsync((void **)&ws, (size_t)grid * 2 * E * sizeof(double), stream);
     if (e != hipSuccess) return e;
-#ifndef LDPC_F64_WS_SOFT
+#if !LDPC_SOFT
     hipLaunchKernelGGL((decode_ms_f64_kernel<CODE, F64_THREADS>), dim3(grid), dim3(F64_THREADS), 0, stream, llrs, output, iters,
                        success, ws, (uint32_t)batch, maxiters);
 #else
@@ -178,5 +174,38 @@ hipError_t launch_f64(const double *llrs, uint8_t *output, uint32_t *iters, uint
 }
 
 }  // namespace
+
+// variant: 0 = tuned default (F64_TUNED); 100 = the workspace kernel above; otherwise the register kernel with IPT = variant & 15,
+// the register-lean check phase if variant & 16, in-place messages if variant & 32.
+// The in-place register kernels (TM8192's default) keep the marginals of the exchanged columns only as sign words in LDS, so they
+// have no soft form: an explicit in-place variant is refused (hipErrorInvalidConfiguration), and the DEFAULT soft decode of a code
+// whose tuned kernel is in place runs the workspace kernel -- its non-in-place register kernel would need 176 KB of LDS, more than
+// a CU has.
+template <>
+hipError_t launch_decode_ms<double, LDPC_SOFT>(int code, int variant, const double *llrs, double *app, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
+{
+    if (batch == 0) return hipSuccess;
+    if (!valid_code(code)) return hipErrorInvalidValue;
+    if (variant >= 0) variant &= ~VARIANT_FLAGS;           // (the f64 kernels always draw from the launch's queue)
+    if (variant == 0) variant = LDPC_SOFT && (F64_TUNED[code] & 32) ? 100 : F64_TUNED[code];
+    if (variant != 100) {
+        if (LDPC_SOFT && (variant & 32)) return hipErrorInvalidConfiguration;
+        return launch_decode_ms_f64_reg<LDPC_SOFT>(code, variant & 15, (variant & 32) ? 2 : ((variant & 16) ? 1 : 0), llrs, app, output,
+                                                   iters, success, batch, maxiters, stream);
+    }
+    switch (code) {
+        case TC128:  return launch_f64<TC128>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TC256:  return launch_f64<TC256>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TC512:  return launch_f64<TC512>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TM1280: return launch_f64<TM1280>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TM1536: return launch_f64<TM1536>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TM2048: return launch_f64<TM2048>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TM5120: return launch_f64<TM5120>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TM6144: return launch_f64<TM6144>(llrs, app, output, iters, success, batch, maxiters, stream);
+        case TM8192: return launch_f64<TM8192, 1024, 256>(llrs, app, output, iters, success, batch, maxiters, stream);   // 0.122 vs 0.081 M/s at 256 threads x 1024 workgroups
+        default: return hipErrorInvalidValue;
+    }
+}
 
 }  // namespace ldpc

@@ -1,14 +1,15 @@
 // decode_ms_i8.hip -- i8 instantiations of the min-sum kernel (decode_ms::<i8>,
 // /root/reference/src/decoder.rs:42-50, :347-475; C entry capi/src/lib.rs:97-103).
+// With -DLDPC_SOFT=1 (decode_ms_soft_i8.o): the soft-output forms of the f32-pipe kernels -- the ones the default dispatch takes for
+// small or unaligned batches.  The bit-sliced kernels keep no marginals once a parity vote is taken (decode_ms_bitslice.hpp;
+// DESIGN.md "Soft output"), so `variant` 64 (LABRADOR_LDPC_HIP_VARIANT_BITSLICE) has no soft form.
 #include "decode_ms_launch.hpp"
-#include "decode_ms_tables.hpp"
 
 namespace ldpc {
 
-// code -> default and alternative indices per thread (decode_ms_tables.hpp: one table for the dispatch, decode_ms_reads_llrs_once
-// and the soft-output dispatch)
-#define LDPC_TABLE LDPC_TABLE_I8
+constexpr int VARIANT_BITSLICE = 64;
 
+#if !LDPC_SOFT
 // The bit-sliced kernel (decode_ms_bs.hip, decode_ms_bitslice.hpp): `variant` 64, and the DEFAULT for the TM codes from
 // bitslice_min_batch() frames up -- one wave (rate 4/5: two) decodes a group of 64 / (M/32) codewords on its own, so it needs a few
 // thousand groups in flight to fill the chip and takes ~3x as long per codeword as a whole workgroup of the f32-pipe kernels: small
@@ -17,7 +18,6 @@ hipError_t launch_decode_ms_bitsliced(int code, const int8_t *llrs, uint8_t *out
                                       uint32_t maxiters, hipStream_t stream, int refill);
 // the launch queue's word for the bit-sliced refill kernels (decode_ms_bs.hip does not see decode_ms_launch.hpp)
 namespace bs { uint32_t *bs_queue_word(hipStream_t stream) { return claim_counter(stream); } }
-constexpr int VARIANT_BITSLICE = 64;
 // groups of 64 / (M/32) codewords from which the bit-sliced kernel is faster per call (tools/bs_crossover.py,
 // profiles/r05_kbench/bs_crossover.txt: TM8192 and TM1280 cross at 1024 groups, TM6144 and TM5120 at 768, TM2048 and TM1536 at 2048)
 constexpr size_t bitslice_min_batch(int code)
@@ -36,7 +36,7 @@ enum class I8Kernel { NONE, BITSLICED, BITSLICED_SPLIT, PAIR, PIPE };
 static bool pipe_variant_built(int code, int variant)          // an explicit indices-per-thread value of the table above
 {
     switch (code) {
-        LDPC_TABLE(LDPC_BUILT_CASE)
+        LDPC_TABLE_I8(LDPC_BUILT_CASE)
         default: return false;
     }
 }
@@ -79,38 +79,33 @@ const char *decode_ms_i8_kernel_name(int code, int variant, size_t batch)
     }
 }
 
+#endif
+
 template <>
-hipError_t launch_decode_ms<int8_t>(int code, int variant, const int8_t *llrs, uint8_t *output,
-                                    uint32_t *iters, uint8_t *success, size_t batch,
-                                    uint32_t maxiters, hipStream_t stream)
+hipError_t launch_decode_ms<int8_t, LDPC_SOFT>(int code, int variant, const int8_t *llrs, int8_t *app, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
 {
     LDPC_SPLIT_VARIANT();
+#if LDPC_SOFT
+    if (!valid_code(code)) return hipErrorInvalidValue;
+    if (variant == VARIANT_BITSLICE) return hipErrorInvalidConfiguration;
+#else
     switch (pick_i8_kernel(code, variant, lflags, batch, bitslice_aligned(llrs, output))) {
         case I8Kernel::BITSLICED:
         case I8Kernel::BITSLICED_SPLIT:
             return launch_decode_ms_bitsliced(code, llrs, output, iters, success, batch, maxiters, stream, i8_refills(code, variant, lflags, batch) ? 1 : 0);
-        case I8Kernel::PAIR:           // TM8192: pair-ownership kernel by default (decode_ms_pair.hpp), `variant` 2 / 4 = the (t, t + M/2) kernel
-            return launch_pair<TM8192, int8_t>(llrs, output, iters, success, batch, maxiters, stream, lflags);
+        case I8Kernel::PAIR:
         case I8Kernel::PIPE:
-            break;
+            break;                     // the f32-pipe kernels: dispatch_pipe below
         default:
             return valid_code(code) ? hipErrorInvalidConfiguration : hipErrorInvalidValue;
     }
-    switch (code) {
-        LDPC_TABLE(LDPC_CASE)
-        default: return hipErrorInvalidValue;
-    }
+#endif
+    return dispatch_pipe<int8_t, LDPC_SOFT>(code, variant, lflags, llrs, app, output, iters, success, batch, maxiters, stream);
 }
 
-template <>
-bool decode_ms_reads_llrs_once<int8_t>(int code, int variant)
-{
-    if (variant != 0) return false;
-    if (code == TM8192) return true;             // the pair kernel holds its LLRs in registers
-    switch (code) {
-        LDPC_TABLE(LDPC_ONCE_CASE)
-        default: return false;
-    }
-}
+#if !LDPC_SOFT
+template bool decode_ms_reads_llrs_once<int8_t>(int, int);
+#endif
 
 }  // namespace ldpc

@@ -1,11 +1,10 @@
 // decode_ms_launch.hpp -- host-side dispatch from (code, variant) to a kernel instantiation.
 //
 // Each LLR type has its own translation unit (decode_ms_f32.hip, ...) so the instantiations
-// compile in parallel; they all expand LDPC_DEFINE_LAUNCHER below.
+// compile in parallel; each is compiled twice, the second time with -DLDPC_SOFT=1 for the soft-output kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <map>
@@ -14,6 +13,14 @@
 
 #include "decode_ms_kernel.hpp"
 #include "decode_ms_pair.hpp"
+#include "decode_ms_tables.hpp"
+#include "occupancy.hpp"
+
+// LDPC_SOFT=1 (Makefile: the decode_ms_soft_*.o objects): the translation unit instantiates the soft-output forms of its kernels,
+// kept out of the hard-only objects, whose kernels stay exactly what they are
+#ifndef LDPC_SOFT
+#define LDPC_SOFT 0
+#endif
 
 namespace ldpc {
 
@@ -21,21 +28,22 @@ namespace ldpc {
 // IPT (indices per thread) for the code; a positive value requests that IPT explicitly and
 // yields hipErrorInvalidConfiguration if it was not instantiated.  VARIANT_STATIC added to either
 // distributes the codewords over the workgroups by a fixed stride instead of through the launch's queue.
-template <class T>
-hipError_t launch_decode_ms(int code, int variant, const T *llrs, uint8_t *output, uint32_t *iters,
+// SOFT: the soft-output kernels, which also write every codeword's marginals (decoder.rs:377) to `app` [batch][n + p] in the
+// LLR type (nullptr without SOFT); hipErrorInvalidConfiguration for a `variant` whose kernel has no soft form (the header lists them).
+template <class T, bool SOFT>
+hipError_t launch_decode_ms(int code, int variant, const T *llrs, T *app, uint8_t *output, uint32_t *iters,
                             uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
 
-// Will launch_decode_ms<T>(code, variant, ...) read every LLR from memory exactly once?  (false for explicit variants, which
+// The f64 register kernels (decode_ms_f64_reg.hip, built as three objects: PART): ipt / lean select the instantiation;
+// hipErrorInvalidConfiguration if it was not built (LEAN 2, in place, has no soft form).
+template <bool SOFT, int PART = 0>
+hipError_t launch_decode_ms_f64_reg(int code, int ipt, int lean, const double *llrs, double *app, uint8_t *output, uint32_t *iters,
+                                    uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
+
+// Will launch_decode_ms<T, false>(code, variant, ...) read every LLR from memory exactly once?  (false for explicit variants, which
 // are not second-guessed, and for forced two-pass NaN handling, whose second kernel reads the first one's marks.)
 template <class T>
 bool decode_ms_reads_llrs_once(int code, int variant);
-
-// The same decode with soft output: `app` [batch][n + p] receives every codeword's marginals (decoder.rs:377) in the LLR type, and
-// output / iters / success are those of launch_decode_ms<T>.  hipErrorInvalidConfiguration for a `variant` whose kernel has no
-// soft form (decode_ms_soft_*.hip; the header lists them).
-template <class T>
-hipError_t launch_decode_ms_soft(int code, int variant, const T *llrs, T *app, uint8_t *output, uint32_t *iters,
-                                 uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
 
 // Largest |LLR| for which the f32 kernels may drop the FLT_MAX clamp of the exclusive minimum
 // (decoder.rs:414-415) for a run of `maxiters` iterations.  The clamp acts only if a magnitude overflows to
@@ -131,27 +139,16 @@ inline uint32_t *claim_counter(hipStream_t stream)
     return head;
 }
 
-// Resident workgroups per device for one instantiation (occupancy x compute units), cached.
-template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM, int NANPASS = 0, bool SOFT = false>
-int resident_workgroups()
+// The grid of a persistent launch over `work` items (codeword groups, chunks of them, codewords).  Where one workgroup fills a CU
+// (TM8192) the grid is exactly the resident set: each workgroup then decodes hundreds of codewords and the data-dependent
+// iteration counts average out.  Where several fit per CU the grid is 16x the resident set so that the hardware dispatcher
+// still balances (measured on TM2048: 21.7 / 25.0 / 27.2 / 27.7 M codewords/s at 1x / 2x / 8x / 64x).  With the launch's
+// queue (`queued`: claim_counter) the grid is the resident set itself: the workgroups balance the work by drawing from the
+// queue, and nothing is paid for starting workgroups beyond the first wave of them.
+inline size_t persistent_grid(size_t resident, bool queued, size_t work)
 {
-    using GEO = Geometry<CODE, T, IPT>;
-    static std::atomic<int> cached[64] = {};     // concurrent callers may both fill an entry: they store the same value
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int v = cached[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        int per_cu = 0, cus = 0;
-        hipError_t e;
-        if constexpr (SOFT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, soft_decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG, 0);
-        if (e != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        v = per_cu * cus;
-        cached[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
+    const size_t grid = (resident <= 256 || queued) ? resident : resident * 16;
+    return grid < work ? grid : work;
 }
 
 // Launch one instantiation (IPT indices per thread; LEAN 1 = register-lean check phase, 2 = in-place messages).
@@ -169,18 +166,14 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
     if (batch == 0) return hipSuccess;
     const size_t groups = (batch + GEO::G - 1) / GEO::G;
     if (batch > 0xFFFFFFFFull || groups > 0x7FFFFFFFull) return hipErrorInvalidValue;   // (capi.hip slices larger batches)
-    // Persistent workgroups with a static stride over the codeword groups.  Where one workgroup
-    // fills a CU (TM8192) the grid is exactly the resident set: each workgroup then decodes
-    // hundreds of codewords and the data-dependent iteration counts average out.  Where several
-    // fit per CU the grid is 16x the resident set so that the hardware dispatcher still balances
-    // (measured on TM2048: 21.7 / 25.0 / 27.2 / 27.7 M codewords/s at 1x / 2x / 8x / 64x).
-    // With the launch's queue (claim_counter) the grid is the resident set itself: the workgroups balance the work by
-    // drawing from the queue, and nothing is paid for starting workgroups beyond the first wave of them.
-    // Which distribution: the queue for workgroups of 8 waves and more (TM2048 +3.0 %, TM5120 +1.4-1.8 %, TM8192 +0.9 % over
-    // the fixed stride: their decodes take tens of microseconds and a workgroup is expensive to start); the fixed stride on
-    // the 16x grid for the smaller ones, where the hardware dispatcher is a queue that costs no atomics (the TC codes' draws
-    // would hit the device's ceiling of ~85 M same-address atomics per second: claim_chunk()).
-    const size_t resident = (size_t)resident_workgroups<CODE, T, IPT, PF, LEAN, FORM, NANPASS, SOFT>();
+    // Persistent workgroups over the codeword groups (persistent_grid).  Which distribution: the queue for workgroups of 8 waves
+    // and more (TM2048 +3.0 %, TM5120 +1.4-1.8 %, TM8192 +0.9 % over the fixed stride: their decodes take tens of microseconds
+    // and a workgroup is expensive to start); the fixed stride on the 16x grid for the smaller ones, where the hardware dispatcher
+    // is a queue that costs no atomics (the TC codes' draws would hit the device's ceiling of ~85 M same-address atomics per
+    // second: claim_chunk()).
+    size_t resident;
+    if constexpr (SOFT) resident = resident_workgroups<soft_decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG>();
+    else resident = resident_workgroups<decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG>();
     constexpr bool queue_fed = GEO::WG >= 512;
     uint32_t *claim = (static_stride || maxiters == 0 || !queue_fed) ? nullptr : claim_counter(stream);
     // groups per draw: at least ~8 draws per resident workgroup, so that the last chunks are a small part of a short launch
@@ -189,9 +182,7 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
         K = claim_chunk<CODE, T, IPT>();
         while (K > 1 && groups < 8 * K * resident) K /= 2;
     }
-    const size_t chunks = (groups + K - 1) / K;
-    size_t grid = (resident <= 256 || claim != nullptr) ? resident : resident * 16;
-    if (grid > chunks) grid = chunks;
+    size_t grid = persistent_grid(resident, claim != nullptr, (groups + K - 1) / K);
     if constexpr (NANPASS == 2) {                // one round of workgroups, each looking at 64 marks per load
         grid = resident < (groups + 63) / 64 ? resident : (groups + 63) / 64;
     }
@@ -250,7 +241,10 @@ hipError_t launch_cfg(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *
     if constexpr (two_pass_nan<CODE, T, IPT, LEAN>()) {
         constexpr int FORM = selfcorr_med3<CODE, T>();
         static_assert(!has_nocap_loop<CODE, T, IPT, LEAN>());
-        bool two = batch >= 2 * (size_t)resident_workgroups<CODE, T, IPT, false, LEAN, FORM, 1, SOFT>();
+        int resident;
+        if constexpr (SOFT) resident = resident_workgroups<soft_decode_ms_kernel<CODE, T, IPT, false, LEAN, FORM, 1>, Geometry<CODE, T, IPT>::WG>();
+        else resident = resident_workgroups<decode_ms_kernel<CODE, T, IPT, false, LEAN, FORM, 1>, Geometry<CODE, T, IPT>::WG>();
+        bool two = batch >= 2 * (size_t)resident;
         if (lflags & LF_TWO_PASS) two = true;
         if ((lflags & LF_ONE_PASS) || maxiters == 0 || maxiters == NAN_MARK) two = false;
         if (two) {
@@ -311,23 +305,11 @@ hipError_t launch_pair_form(const T *llrs, uint8_t *output, uint32_t *iters, uin
                             size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags, T *app = nullptr)
 {
     using GEO = PairGeometry<CODE, T>;
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int resident = cached[dev].load(std::memory_order_relaxed);
-    if (resident == 0) {
-        int per_cu = 0, cus = 0;
-        hipError_t e;
-        if constexpr (SOFT) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, soft_decode_ms_pair_kernel<CODE, T, FORM>, GEO::NT, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_pair_kernel<CODE, T, FORM>, GEO::NT, 0);
-        if (e != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = per_cu * cus;
-        cached[dev].store(resident, std::memory_order_relaxed);
-    }
+    size_t resident;
+    if constexpr (SOFT) resident = resident_workgroups<soft_decode_ms_pair_kernel<CODE, T, FORM>, GEO::NT>();
+    else resident = resident_workgroups<decode_ms_pair_kernel<CODE, T, FORM>, GEO::NT>();
     uint32_t *claim = ((lflags & LF_STATIC) != 0 || maxiters == 0) ? nullptr : claim_counter(stream);
-    size_t grid = (resident <= 256 || claim != nullptr) ? (size_t)resident : (size_t)resident * 16;
-    if (grid > batch) grid = batch;
+    const size_t grid = persistent_grid(resident, claim != nullptr, batch);
     constexpr bool clamp_form = std::is_same_v<T, float> && FORM == 2;
     if constexpr (SOFT)
         hipLaunchKernelGGL((soft_decode_ms_pair_kernel<CODE, T, FORM>), dim3((unsigned)grid), dim3(GEO::NT), 0, stream,
@@ -357,25 +339,17 @@ hipError_t launch_pair(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t 
 }
 
 // one `case` of the dispatch switch: default IPT plus optional alternatives
-// (expects `variant` with VARIANT_STATIC already split off into `static_stride`: LDPC_SPLIT_VARIANT)
+// (expects `variant` with VARIANT_STATIC already split off into `static_stride`: LDPC_SPLIT_VARIANT; and SOFT, app)
 #define LDPC_CASE(CODE, T, DEF, ...)                                                             \
     case CODE: {                                                                                 \
         constexpr int alts[] = {DEF, ##__VA_ARGS__};                                             \
-        return dispatch_ipt<CODE, T, DEF, ##__VA_ARGS__>(variant == 0 ? alts[0] : variant, llrs, \
-                                                         output, iters, success, batch, maxiters, \
-                                                         stream, lflags);                        \
+        return dispatch_ipt<CODE, T, SOFT, DEF, ##__VA_ARGS__>(variant == 0 ? alts[0] : variant, \
+                                                               llrs, app, output, iters, success, \
+                                                               batch, maxiters, stream, lflags);  \
     }
 // the same table row as a `case` of decode_ms_reads_llrs_once<T>(): the DEFAULT kernel of the code
 #define LDPC_ONCE_CASE(CODE, T, DEF, ...)                                                        \
     case CODE: return kernel_reads_llrs_once<T, lean_mode<CODE, T, DEF>()>();
-// ... and of launch_decode_ms_soft<T>(): the soft-output forms of the same kernels
-#define LDPC_SOFT_CASE(CODE, T, DEF, ...)                                                        \
-    case CODE: {                                                                                 \
-        constexpr int alts[] = {DEF, ##__VA_ARGS__};                                             \
-        return dispatch_ipt_soft<CODE, T, DEF, ##__VA_ARGS__>(variant == 0 ? alts[0] : variant,  \
-                                                              llrs, app, output, iters, success, \
-                                                              batch, maxiters, stream, lflags);  \
-    }
 #define LDPC_SPLIT_VARIANT()                                                                     \
     unsigned lflags = 0;                                                                         \
     if (variant >= 0) {                                                                          \
@@ -384,25 +358,67 @@ hipError_t launch_pair(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t 
         if (variant & VARIANT_TWO_PASS) lflags |= LF_TWO_PASS;                                   \
         variant &= ~VARIANT_FLAGS;                                                               \
     }
+// a switch over `code` with one CASE(CODE, T, DEF, ALTS...) per row of T's table (decode_ms_tables.hpp)
+#define LDPC_TABLE_SWITCH(T, CASE)                                                               \
+    if constexpr (std::is_same_v<T, float>) switch (code) { LDPC_TABLE_F32(CASE) }               \
+    else if constexpr (std::is_same_v<T, int8_t>) switch (code) { LDPC_TABLE_I8(CASE) }          \
+    else if constexpr (std::is_same_v<T, int16_t>) switch (code) { LDPC_TABLE_I16(CASE) }        \
+    else if constexpr (std::is_same_v<T, int32_t>) switch (code) { LDPC_TABLE_I32(CASE) }
 
-template <int CODE, class T, int... IPTS>
-hipError_t dispatch_ipt(int ipt, const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
+template <int CODE, class T, bool SOFT, int... IPTS>
+hipError_t dispatch_ipt(int ipt, const T *llrs, T *app, uint8_t *output, uint32_t *iters, uint8_t *success,
                         size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
 {
     hipError_t r = hipErrorInvalidConfiguration;
-    (void)((ipt == IPTS ? (r = launch_one<CODE, T, IPTS>(llrs, output, iters, success, batch, maxiters, stream, lflags), true)
+    (void)((ipt == IPTS ? (r = launch_one<CODE, T, IPTS, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app), true)
                         : false) || ...);
     return r;
 }
 
-template <int CODE, class T, int... IPTS>
-hipError_t dispatch_ipt_soft(int ipt, const T *llrs, T *app, uint8_t *output, uint32_t *iters, uint8_t *success,
-                             size_t batch, uint32_t maxiters, hipStream_t stream, unsigned lflags)
+// The f32-pipe dispatch of an integer or f32 LLR type, `variant` split by LDPC_SPLIT_VARIANT: the pair-ownership kernel
+// (decode_ms_pair.hpp) for TM8192 by default (f32 6.7 vs 6.35 M codewords/s) and for `variant` 32 (TM8192, and TM2048 for f32;
+// for TM6144 the compiler's control-flow structurizer turns its four quarter bodies into EXEC-masked loops -- 100x slower, so it
+// is not built), otherwise the type's table: `variant` 2 / 4 = the (t, t + M/2) kernel with that many indices per thread.
+template <class T, bool SOFT>
+hipError_t dispatch_pipe(int code, int variant, unsigned lflags, const T *llrs, T *app, uint8_t *output, uint32_t *iters,
+                         uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
 {
-    hipError_t r = hipErrorInvalidConfiguration;
-    (void)((ipt == IPTS ? (r = launch_one<CODE, T, IPTS, true>(llrs, output, iters, success, batch, maxiters, stream, lflags, app), true)
-                        : false) || ...);
-    return r;
+    if (variant == VARIANT_PAIR || (variant == 0 && code == TM8192)) {
+        if (code == TM8192) return launch_pair<TM8192, T, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
+        if constexpr (std::is_same_v<T, float>)
+            if (code == TM2048) return launch_pair<TM2048, T, SOFT>(llrs, output, iters, success, batch, maxiters, stream, lflags, app);
+        return hipErrorInvalidConfiguration;
+    }
+    LDPC_TABLE_SWITCH(T, LDPC_CASE)
+    return hipErrorInvalidValue;
 }
+
+// f32, i16, i32 (decode_ms_<type>.hip); i8 and f64 have dispatches of their own
+template <class T, bool SOFT>
+hipError_t launch_decode_ms(int code, int variant, const T *llrs, T *app, uint8_t *output, uint32_t *iters,
+                            uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
+{
+    LDPC_SPLIT_VARIANT();
+    return dispatch_pipe<T, SOFT>(code, variant, lflags, llrs, app, output, iters, success, batch, maxiters, stream);
+}
+
+// every type but f64 (decode_ms_f64.hip)
+template <class T>
+bool decode_ms_reads_llrs_once(int code, int variant)
+{
+    if (variant != 0) return false;
+    if (code == TM8192) return true;             // the pair kernel holds its LLRs in registers
+    LDPC_TABLE_SWITCH(T, LDPC_ONCE_CASE)
+    return false;
+}
+
+// The heavy f32 instantiations, compiled as three objects of their own (decode_ms_f32_part.hip, -DF32_PART=1/2/3) so that the build
+// stays parallel (decode_ms_f32.hip alone took 3 min 40 s of a 4 min build); decode_ms_f32.hip declares them `extern template`.
+// LDPC_F32_PART_<n>(X, SOFT) applies X to every launcher of part n.
+#define LDPC_F32_SIG (const float *, uint8_t *, uint32_t *, uint8_t *, size_t, uint32_t, hipStream_t, unsigned, float *)
+#define LDPC_F32_PART_1(X, SOFT) X(launch_pair<TM8192, float, SOFT>)             /* the metric's kernel, both clamp forms */
+#define LDPC_F32_PART_2(X, SOFT) X(launch_pair<TM2048, float, SOFT>) X(launch_one<TM8192, float, 2, SOFT>) X(launch_one<TM8192, float, 4, SOFT>)
+#define LDPC_F32_PART_3(X, SOFT) X(launch_one<TM5120, float, 1, SOFT>)  /* one-pass kernel and the two NaN passes (two_pass_nan()) */ \
+                                 X(launch_one<TM6144, float, 1, SOFT>) X(launch_one<TM6144, float, 2, SOFT>)
 
 }  // namespace ldpc

@@ -13,23 +13,9 @@ hipError_t launch_layered(const float *llrs, float *app, uint8_t *output, uint32
     if (batch == 0) return hipSuccess;
     const size_t groups = (batch + GEO::G - 1) / GEO::G;
     if (batch > 0xFFFFFFFFull || groups > 0x7FFFFFFFull) return hipErrorInvalidValue;   // (capi.hip slices larger batches)
-    static std::atomic<int> cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int resident = cached[dev].load(std::memory_order_relaxed);
-    if (resident == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_layered_kernel<CODE, SOFT>, GEO::WG, 0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = per_cu * cus;
-        cached[dev].store(resident, std::memory_order_relaxed);
-    }
-    // as launch_cfg_form: the launch's queue for workgroups of 8 waves and more (the grid is then the resident set), a fixed stride
-    // over a 16x grid for the smaller ones
+    const size_t resident = resident_workgroups<decode_ms_layered_kernel<CODE, SOFT>, GEO::WG>();
     uint32_t *claim = (maxiters == 0 || GEO::WG < 512) ? nullptr : claim_counter(stream);
-    size_t grid = (resident <= 256 || claim != nullptr) ? (size_t)resident : (size_t)resident * 16;
-    if (grid > groups) grid = groups;
+    const size_t grid = persistent_grid(resident, claim != nullptr, groups);
     hipLaunchKernelGGL((decode_ms_layered_kernel<CODE, SOFT>), dim3((unsigned)grid), dim3(GEO::WG), 0, stream,
                        llrs, app, output, iters, success, (uint32_t)batch, maxiters, claim);
     return hipGetLastError();
