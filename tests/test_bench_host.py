@@ -264,3 +264,12 @@ def test_whole_job_check_against_the_committed_answers():
     assert len({b.job_key("TM8192", "f32", 4194304, e, m, p) for e in (2.0, 2.5) for m in (25, 50) for p in (256, 16)}) == 8
     for k, v in b.EXPECTED_JOBS.items():
         assert set(v) == {"iters_sum", "failed_frames", "job_digest"} and len(v["job_digest"]) == 14 and int(v["job_digest"], 16) < b.DIGEST_MOD, k
+
+
+def test_the_corruption_hook_needs_the_full_run():
+    """--corrupt-frame exists to void a line through the whole-job check, which only --full runs: without it the hook would do
+    nothing, so the command line is refused before anything starts."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--corrupt-frame", "3"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--corrupt-frame" in r.stderr and "--full" in r.stderr, r.stderr

@@ -41,7 +41,7 @@ def _check(d, world, total):
 
 def test_four_ranks_on_one_gpu_started_by_bench_py():
     r = subprocess.run([sys.executable, BENCH, "--gpus", str(MAX_RANKS), "--devices", ",".join(["0"] * MAX_RANKS), "--total-frames", "65536",
-                        "--steps", "2", "--warmup", "1", "--rank-parity-frames", "32", "--no-configs"], capture_output=True, text=True, cwd=ROOT,
+                        "--steps", "2", "--warmup", "1", "--rank-parity-frames", "32", "--no-configs", "--full"], capture_output=True, text=True, cwd=ROOT,
                        timeout=1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     _check(_one_json_line(r.stdout), MAX_RANKS, 65536)
@@ -53,7 +53,7 @@ def test_two_ranks_under_the_drivers_launcher():
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), BENCH, "--gpus", "2", "--devices", "0,0", "--total-frames", "32769", "--steps", "2",
-                        "--warmup", "1", "--rank-parity-frames", "32", "--no-configs"], capture_output=True, text=True, cwd=ROOT, timeout=1500)
+                        "--warmup", "1", "--rank-parity-frames", "32", "--no-configs", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     _check(_one_json_line(r.stdout), 2, 32769)            # an odd total: the shards differ by one frame
 
@@ -61,7 +61,7 @@ def test_two_ranks_under_the_drivers_launcher():
 def test_ranks_that_each_see_one_visible_device():
     env = dict(os.environ, HIP_VISIBLE_DEVICES="0")
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--total-frames", "16384", "--steps", "1", "--warmup", "1",
-                        "--rank-parity-frames", "32", "--no-configs"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=1500)
+                        "--rank-parity-frames", "32", "--no-configs", "--full"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     _check(_one_json_line(r.stdout), 2, 16384)
 
@@ -74,7 +74,7 @@ def test_an_n_gpu_job_is_the_one_gpu_job_bit_for_bit():
     total, seen = 40961, {}
     for world in (1, 2, 3, MAX_RANKS):
         r = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--devices", ",".join(["0"] * world), "--total-frames", str(total),
-                            "--steps", "1", "--warmup", "0", "--no-cpu", "--no-configs"], capture_output=True, text=True, cwd=ROOT, timeout=1500)
+                            "--steps", "1", "--warmup", "0", "--no-cpu", "--no-configs", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=1500)
         assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
         d = _one_json_line(r.stdout)
         assert d["n_gpus"] == world and d["config"]["total_frames"] == total
@@ -89,7 +89,7 @@ def test_the_i8_jobs_verify_themselves_too(dtype, code, ebn0):
     """The bit-sliced i8 kernels behind the same self-check: 1 and 3 ranks reproduce the committed answers of the 40 961-frame jobs."""
     for world in (1, 3):
         r = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--devices", ",".join(["0"] * world), "--code", code, "--dtype", dtype,
-                            "--ebn0", str(ebn0), "--total-frames", "40961", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-configs"],
+                            "--ebn0", str(ebn0), "--total-frames", "40961", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-configs", "--full"],
                            capture_output=True, text=True, cwd=ROOT, timeout=1500)
         assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
         d = _one_json_line(r.stdout)
@@ -101,7 +101,7 @@ def test_a_corrupted_shard_voids_the_line(world, frame):
     """One flipped output bit in ONE frame of one rank's shard (bench.py --corrupt-frame, a test hook), outside every rank's oracle
     sample: the whole-job digest no longer equals the committed one, the line says so, carries no value, and bench exits non-zero."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--devices", ",".join(["0"] * world), "--total-frames", "40961", "--steps", "1",
-                        "--warmup", "0", "--rank-parity-frames", "32", "--no-configs", "--corrupt-frame", str(frame)],
+                        "--warmup", "0", "--rank-parity-frames", "32", "--no-configs", "--full", "--corrupt-frame", str(frame)],
                        capture_output=True, text=True, cwd=ROOT, timeout=1500)
     assert r.returncode != 0, r.stdout[-2000:]
     d = _one_json_line(r.stdout)
@@ -119,7 +119,7 @@ def test_dump_outputs_hold_the_job_the_line_verified(tmp_path):
 
     def run(world, total, outdir):
         r = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--devices", ",".join(["0"] * world), "--total-frames", str(total),
-                            "--steps", "2", "--warmup", "0", "--no-cpu", "--no-configs", "--dump-outputs", str(outdir)],
+                            "--steps", "2", "--warmup", "0", "--no-cpu", "--no-configs", "--full", "--dump-outputs", str(outdir)],
                            capture_output=True, text=True, cwd=ROOT, timeout=1500)
         assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
         files = {n: np.load(outdir / f"{n}.npy") for n in ("output", "iters", "success")}
@@ -140,3 +140,30 @@ def test_dump_outputs_hold_the_job_the_line_verified(tmp_path):
     _, three = run(3, 40961, tmp_path / "three")
     assert one["output"].shape[0] < 40961
     assert all((one[n] == three[n]).all() for n in one)
+
+
+def test_a_plain_run_prints_the_headline_alone(tmp_path):
+    """Without --full a run sets up, warms up, times its steps, dumps and prints: the line holds the contract's fields and the
+    configuration, nothing that takes work of its own.  Its dumped outputs are those of a --full run of the same job, on one
+    rank and on two."""
+    import numpy as np
+    plain_keys = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                  "dtype", "data", "config"}
+
+    def run(world, outdir, *extra):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--devices", ",".join(["0"] * world), "--total-frames", "16384",
+                            "--steps", "2", "--warmup", "1", "--dump-outputs", str(outdir), *extra], capture_output=True, text=True, cwd=ROOT,
+                           timeout=1500)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        return _one_json_line(r.stdout), {n: np.load(outdir / f"{n}.npy") for n in ("output", "iters", "success")}
+
+    full, want = run(1, tmp_path / "full", "--full", "--no-cpu", "--no-configs")
+    assert full["parity"]["whole_job"]["match"] is True, full["parity"]["whole_job"]
+    for world in (1, 2):
+        d, got = run(world, tmp_path / f"plain{world}")
+        assert set(d) == plain_keys, sorted(d)
+        assert d["n_gpus"] == world and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "codewords/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["metric"] == full["metric"] and d["config"]["total_frames"] == 16384
+        assert d["config"] == full["config"] if world == 1 else d["config"]["library_build"] == full["config"]["library_build"]
+        assert all((got[n] == want[n]).all() for n in want)

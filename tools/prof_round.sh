@@ -6,8 +6,8 @@ set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-r06_final}; mkdir -p $O
 rm -rf $O/trace $O/*.pmc[1-5]          # a re-run must not leave an older run's files beside the new ones
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --no-cpu > $O/trace_bench.log 2>&1
+python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --no-cpu > $O/trace_bench.log 2>&1
 pmc() {   # tag, bench args...: five counter passes on short runs of one configuration
   tag=$1; shift
   B="python3 $R/bench.py --no-cpu --no-configs --steps 2 --warmup 1 $*"

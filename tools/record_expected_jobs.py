@@ -28,7 +28,7 @@ def main():
     out = {}
     for code, dtype, total, ebn0 in JOBS:
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--code", code, "--dtype", dtype, "--total-frames", str(total),
-                            "--ebn0", str(ebn0), "--steps", "1", "--warmup", "0", "--no-cpu", "--no-configs"], capture_output=True, text=True)
+                            "--ebn0", str(ebn0), "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--no-configs"], capture_output=True, text=True)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if not lines:
             print(f"{code} {dtype} {total}: no line (rc {r.returncode}): {r.stderr[-500:]}", file=sys.stderr)

@@ -19,7 +19,7 @@ for r in rows:
         continue
     k = re.sub(r"^void ldpc::", "", k).split("(")[0]
     by.setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
-out = [f"rocprofv3 --kernel-trace of `python bench.py --no-cpu` (the default command; --steps 5 --warmup 1) on library build {build},",
+out = [f"rocprofv3 --kernel-trace of `python bench.py --full --no-cpu` (--steps 5 --warmup 1) on library build {build},",
        "per-dispatch durations in launch order, ms:", ""]
 for k, d in by.items():
     out.append(f"{k}: {len(d)} launches")
