@@ -60,9 +60,11 @@ class Structure:
             fill[c] += 1
 
 
-def decode_ms(st: Structure, llrs: np.ndarray, n: int, maxiters: int):
+def decode_ms(st: Structure, llrs: np.ndarray, n: int, maxiters: int, return_va: bool = False):
     """llrs [frames, n] of dtype i8/i16/i32/f32/f64 -> (output [frames, (n+p)/8] u8, iters [frames] u32,
-    success [frames] u8), each frame exactly as LDPCCode::decode_ms would return it."""
+    success [frames] u8), each frame exactly as LDPCCode::decode_ms would return it.  return_va: a fourth
+    result, the marginals va [frames, n + p] in the LLR type as the reference leaves them in its working
+    area (:377) -- those of the converging iteration, of the last one on failure, all zero for maxiters 0."""
     llrs = np.ascontiguousarray(llrs)
     dt = llrs.dtype
     F = llrs.shape[0]
@@ -96,6 +98,7 @@ def decode_ms(st: Structure, llrs: np.ndarray, n: int, maxiters: int):
     min2 = np.zeros((F, C), dtype=wt)
     sgn = np.zeros((F, C), dtype=bool)
     va = np.zeros((F, V), dtype=wt)
+    va_out = np.zeros((F, V), dtype=dt)
     live = np.arange(F)                           # frames still iterating (row i of the state = frame live[i])
     L = llrs.astype(wt)
 
@@ -136,10 +139,14 @@ def decode_ms(st: Structure, llrs: np.ndarray, n: int, maxiters: int):
         if done.any():
             fr = live[done]
             output[fr] = hard_pack(va[done])
+            va_out[fr] = va[done]                 # (integers: already saturated to the type)
             iters[fr] = it                        # 0-based index of the converging iteration (:462)
             success[fr] = 1
             stay = ~done
             live, v, min1, min2, sgn, va = live[stay], v[stay], min1[stay], min2[stay], sgn[stay], va[stay]
     if len(live):
         output[live] = hard_pack(va)              # failure: hard decision of the last marginals (:466-474)
+        va_out[live] = va
+    if return_va:
+        return output, iters, success, va_out
     return output, iters, success

@@ -150,6 +150,47 @@ def decode_ms_batch(code, llrs: np.ndarray, maxiters: int, nthreads: int = 0, li
     return out, iters, succ, used
 
 
+def _soft_threads() -> int:
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    return max(1, min(16, cpus))
+
+
+def decode_ms_soft_batch(code, llrs: np.ndarray, maxiters: int):
+    """[batch, n] -> (output[batch, output_len], iters[batch] u32, success[batch] u8, va[batch, n + p]): the hard results as
+    decode_ms_batch reports them (iters = maxiters on failure) and the marginals va (src/decoder.rs:377) each frame's decode leaves
+    in the working area, in the LLR type.  Frames go through the single-frame entry on a pool of at most 16 threads (ctypes
+    releases the GIL for the call)."""
+    from concurrent.futures import ThreadPoolExecutor
+    code = int(code)
+    llrs = np.ascontiguousarray(llrs)
+    assert llrs.ndim == 2 and llrs.shape[1] == n(code)
+    s = _SUF[llrs.dtype]
+    fn = getattr(L, "oracle_decode_ms_" + s)
+    B, E, V = llrs.shape[0], L.oracle_code_paritycheck_sum(code), n(code) + p(code)
+    out = np.zeros((B, output_len(code)), dtype=np.uint8)
+    iters = np.zeros(B, dtype=np.uint32)
+    succ = np.zeros(B, dtype=np.uint8)
+    va = np.zeros((B, V), dtype=llrs.dtype)
+    wlen, w8len = L.oracle_ms_working_len(code), L.oracle_ms_working_u8_len(code)
+
+    def one(f):
+        w = np.zeros(wlen, dtype=llrs.dtype)
+        w8 = np.zeros(w8len, dtype=np.uint8)
+        it = ctypes.c_size_t(0)
+        ok = fn(code, llrs[f].ctypes.data, out[f].ctypes.data, w.ctypes.data, w8.ctypes.data, maxiters, ctypes.byref(it))
+        assert ok >= 0
+        iters[f] = it.value if ok else maxiters
+        succ[f] = 1 if ok else 0
+        va[f] = w[2 * E: 2 * E + V]
+
+    with ThreadPoolExecutor(max_workers=min(_soft_threads(), max(B, 1))) as ex:
+        list(ex.map(one, range(B)))
+    return out, iters, succ, va
+
+
 def hard_to_llrs(code, hard: np.ndarray, dtype) -> np.ndarray:
     llrs = np.zeros(n(code), dtype=dtype)
     hard = np.ascontiguousarray(hard, dtype=np.uint8)

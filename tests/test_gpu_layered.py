@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import edge_frames
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 import layered_restatement as lr
@@ -235,3 +236,103 @@ def test_ber_harness_schedule_switch():
         perftest.ms_trials(code, 1.7, "ebn0", schedule="nope", **kw)
     assert perftest.main(["--code", "TC128", "--snrs", "3.0", "--noise", "ebn0", "--maxiters", "20", "--batch", "4096",
                           "--max-bits", "1e5", "--schedule", "layered"]) == 0
+
+
+def layered_calls(code, llrs, maxiters, ref=None):
+    """Soft and hard layered calls on the same frames against the restatement (check() compares the soft call's app too)."""
+    ref = ref if ref is not None else lr.decode_layered(structure(code), llrs, maxiters)
+    app, out, it, ok = code.decode_ms_layered_soft_batch(llrs, maxiters)
+    check(code, llrs, maxiters, out, it, ok, app, ref=ref)
+    out_h, it_h, ok_h = code.decode_ms_layered_batch(llrs, maxiters)
+    check(code, llrs, maxiters, out_h, it_h, ok_h, ref=ref)
+    return ref
+
+
+@pytest.mark.parametrize("code", ALL, ids=lambda c: c.name)
+def test_whole_frame_extremes(code):
+    """All +-0.0, every third / fifth zero, denormal frames, sums of finite LLRs that overflow to +-inf, +-inf runs and +-FLT_MAX
+    frames, at caps 1, 3, 25 and 60: a +inf marginal of finite LLRs stays +inf in app."""
+    llrs = edge_frames.whole_frame_rows(code, np.float32, np.random.default_rng(0xF4B + int(code)))
+    saw_inf = False
+    for m in (1, 3, 25, 60):
+        ref = layered_calls(code, llrs, m)
+        saw_inf |= bool(np.isinf(ref[3][[5, 8]]).any())
+    assert saw_inf
+
+
+@pytest.mark.parametrize("code", ALL, ids=lambda c: c.name)
+def test_failing_frames_at_long_caps(code):
+    """Frames that keep failing (0 and 1 dB) next to ones that converge late, at caps 50 and 100."""
+    rng = np.random.default_rng(0x1A7 + int(code))
+    F = 4 if code.n() >= 5120 else 6
+    llrs = np.concatenate([oracle.awgn_llrs(code, rng, F, e, np.float32)[0] for e in (0.0, 1.0, 2.0)])
+    for m in (50, 100):
+        _, it, ok, _ = layered_calls(code, llrs, m)
+        assert (ok == 0).any() and (it[ok == 0] == m).all()
+
+
+def layered_grid_bound(code, cus):
+    """(most frames one round of the layered launch's persistent grid can hold, codewords per group): LayeredGeometry<CODE> (the
+    flooding default's indices per thread: 2 for TM8192, 1 otherwise), the launch's queue for workgroups of 512 threads and more."""
+    nt = code.submatrix_size() // (2 if code == LDPCCode.TM8192 else 1)
+    g = 64 // nt if nt < 64 else 1
+    wg = nt * g
+    return edge_frames.grid_bound(wg, g, wg >= 512, cus), g, wg >= 512
+
+
+@pytest.mark.parametrize("code", ALL, ids=lambda c: c.name)
+def test_persistent_workgroups_decode_many_groups(code):
+    """More codeword groups than the largest grid the launch can have -- the queue-fed kernels (TM2048, TM5120, TM6144, TM8192) and the
+    fixed-stride ones (the TC codes, TM1280, TM1536) -- of mixed kinds (converging, failing, overflowing, NaN, +-FLT_MAX): every frame's
+    app and hard results equal its pool entry's restatement result, in two launches back to back and one on another stream, into
+    prefilled buffers; the hard call on the same batch gives the same hard results."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    bound, g, queued = layered_grid_bound(code, cus)
+    maxiters = 20
+    rng = np.random.default_rng(0x9F + int(code))
+    n, F = code.n(), 12
+    conv = oracle.awgn_llrs(code, rng, F, {0: 5.0, 1: 4.5, 2: 4.0}.get(int(code), 3.5), np.float32)[0]
+    fail = oracle.awgn_llrs(code, rng, F, 0.0, np.float32)[0]
+    over = oracle.awgn_llrs(code, rng, F, 2.0, np.float32)[0] * np.float32(1e37)
+    nan = oracle.awgn_llrs(code, rng, F, 3.0, np.float32)[0]
+    for f in range(F):
+        nan[f, rng.choice(n, size=1 + 3 * f, replace=False)] = np.nan
+    big = np.where(rng.random((F, n)) < 0.5, np.finfo(np.float32).max, -np.finfo(np.float32).max).astype(np.float32)
+    pool = np.concatenate([conv, fail, over, nan, big])
+    kind = np.repeat(np.arange(5), F)
+    ref = lr.decode_layered(structure(code), pool, maxiters)
+    dref = edge_frames.device_ref(ref)
+    frames = bound + bound // 16 + 3
+    assert (frames + g - 1) // g > bound // g
+    idx = edge_frames.batch_of(pool, kind, frames, g, rng)
+    idx_d = torch.from_numpy(idx).cuda()
+    d = torch.from_numpy(pool).cuda()[idx_d].contiguous()
+    np_len = n + code.punctured_bits()
+    tag = f"{code.name} layered ({'queue' if queued else 'fixed stride'})"
+
+    def sentinels():
+        return (torch.full((frames, np_len), -7.0e30, dtype=torch.float32, device="cuda"),
+                torch.full((frames, code.output_len()), 0xEE, dtype=torch.uint8, device="cuda"),
+                torch.full((frames,), -2, dtype=torch.int32, device="cuda"), torch.full((frames,), 7, dtype=torch.uint8, device="cuda"))
+
+    bufs = [sentinels(), sentinels()]
+    torch.cuda.synchronize()
+    for b in bufs:
+        code.decode_ms_layered_soft_batch(d, maxiters, app=b[0], output=b[1], iters=b[2], success=b[3])
+    h = code.decode_ms_layered_batch(d, maxiters)
+    torch.cuda.synchronize()
+    for r, b in enumerate(bufs):
+        edge_frames.check_on_device(f"{tag} run {r}", idx_d, b, dref)
+    for x, y in zip(bufs[0][1:], h):
+        assert torch.equal(x, y), f"{tag}: soft and hard calls differ"
+    del bufs, h
+    b = sentinels()
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        code.decode_ms_layered_soft_batch(d, maxiters, app=b[0], output=b[1], iters=b[2], success=b[3], stream=s.cuda_stream)
+    s.synchronize()
+    edge_frames.check_on_device(f"{tag} second stream", idx_d, b, dref)
+    del b, d, dref, idx_d
+    torch.cuda.empty_cache()

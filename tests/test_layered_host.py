@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import edge_frames
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 import layered_restatement as lr
@@ -33,16 +34,18 @@ def corner_frames(code, rng, frames=5):
 @pytest.mark.parametrize("code", list(LDPCCode), ids=lambda c: c.name)
 def test_one_layer_restatement_is_the_reference_one_iteration_on(code):
     """One layer holding every edge: (success, iters + 1) and output with cap m equal the oracle's with cap m + 1 (iters m against
-    m + 1 on failure), for every frame the reference does not finish at iteration 0 -- AWGN frames at two Eb/N0 and corner values."""
+    m + 1 on failure), and app equals the oracle's va as values (NaN where NaN), for every frame the reference does not finish at
+    iteration 0 -- AWGN frames at two Eb/N0, corner values and the whole-frame edge rows."""
     rng = np.random.default_rng(40 + int(code))
     F = 12 if code.n() >= 5120 else 24
     a, _ = oracle.awgn_llrs(code, rng, F, 1.5, np.float32)
     b, _ = oracle.awgn_llrs(code, rng, F, 2.5, np.float32)
-    llrs = np.concatenate([a, b, corner_frames(code, rng)])
+    llrs = np.concatenate([a, b, corner_frames(code, rng), edge_frames.whole_frame_rows(code, np.float32, rng)])
     st = lr.Structure(int(code), lr.one_layer(oracle.edges(code)[0]))
     compared = 0
     for m in (1, 2, 3, 25):
-        out, it, ok, _ = lr.decode_layered(st, llrs, m)
+        out, it, ok, app = lr.decode_layered(st, llrs, m)
+        _, _, _, va = oracle.decode_ms_soft_batch(code, llrs, m + 1)
         for f in range(len(llrs)):
             ok0, it0, _ = oracle.decode_ms(code, llrs[f], 1)
             if ok0 and it0 == 0:
@@ -51,6 +54,8 @@ def test_one_layer_restatement_is_the_reference_one_iteration_on(code):
             assert bool(ok[f]) == s, (m, f)
             assert int(it[f]) + 1 == (i if s else m + 1), (m, f)
             assert (out[f] == o).all(), (m, f)
+            na, nb = np.isnan(app[f]), np.isnan(va[f])
+            assert (na == nb).all() and (app[f][~na] == va[f][~nb]).all(), (m, f)
             compared += 1
     assert compared >= 4 * len(llrs) // 2
 
@@ -60,8 +65,19 @@ def test_vectorised_and_loop_statements_agree(code):
     rng = np.random.default_rng(7)
     F = 6 if code == LDPCCode.TC128 else 2
     llrs = corner_frames(code, rng, F)
+    _statements_agree(code, llrs, (0, 1, 3, 25))
+
+
+@pytest.mark.parametrize("code", [LDPCCode.TC128, LDPCCode.TM1280], ids=lambda c: c.name)
+def test_vectorised_and_loop_statements_agree_on_whole_frame_rows(code):
+    """All +-0.0, every third / fifth zero, denormal frames, sums that overflow, +-inf runs and +-FLT_MAX frames."""
+    _statements_agree(code, edge_frames.whole_frame_rows(code, np.float32, np.random.default_rng(8)), (1, 3, 25))
+
+
+def _statements_agree(code, llrs, caps):
     st = lr.Structure(int(code))
-    for m in (0, 1, 3, 25):
+    F = len(llrs)
+    for m in caps:
         out, it, ok, app = lr.decode_layered(st, llrs, m)
         for f in range(F):
             o, i, s, a = lr.decode_layered_loop(code, llrs[f], m)
