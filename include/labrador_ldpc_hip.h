@@ -434,8 +434,15 @@ int labrador_ldpc_llrs_to_hard_batch_f64(enum labrador_ldpc_code code, const dou
  * per frame at perftest/src/main.rs:10-18, batched): frame f takes codeword (f mod pool) of
  * `codewords` ([pool][n/8] bytes, MSB first), maps bit b to 1-2b, adds sigma*N(0,1) from a
  * counter-based generator keyed by (seed, f, sample), and writes
- *   f32: the sample itself;   i8: clamp(round(scale*sample), -lim, lim).
- * All pointers are DEVICE memory (opts->memory is ignored); asynchronous on opts->stream. */
+ *   f32: the sample itself;   i8: clamp(rint(scale*sample), -lim, lim), 0 <= lim <= 127 -- the f32 product rounded to the
+ *        nearest integer, ties to even.
+ * The generator is Philox4x32-10 (Salmon et al., SC'11).  Samples 4q .. 4q+3 of frame f come from the one block with the
+ * counter (q, frame_lo, frame_hi, 0) = (q, f mod 2^32, f div 2^32, 0) and the key (seed_lo, seed_hi) = (seed mod 2^32,
+ * seed div 2^32).  Its output words (x, y) make samples 4q and 4q+1, (z, w) make 4q+2 and 4q+3: from a pair (a, b),
+ * u1 = ((a >> 8) + 1) / 2^24, u2 = (b >> 8) / 2^24, r = sqrt(-2 ln u1), and the two normals are r cos(2 pi u2) then
+ * r sin(2 pi u2), evaluated in f32 (so |N| <= 5.77).  A host can regenerate any frame from (seed, f) alone;
+ * tests/channel_reference.py does, and the tests hold the device to it sample by sample.
+ * All pointers are DEVICE memory (opts->memory is ignored), llrs 16-byte aligned; asynchronous on opts->stream. */
 int labrador_ldpc_hip_awgn_f32(enum labrador_ldpc_code code, const uint8_t *codewords, size_t pool,
                                float *llrs, size_t batch, float sigma, uint64_t seed,
                                const struct labrador_ldpc_hip_opts *opts);
