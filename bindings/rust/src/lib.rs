@@ -126,6 +126,8 @@ extern "C" {
     pub fn labrador_ldpc_decode_ms_soft_batch_f64(code: LDPCCode, llrs: *const f64, app: *mut f64, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_layered_batch_f32(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_layered_soft_batch_f32(code: LDPCCode, llrs: *const f32, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_corrected_batch_f32(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32(code: LDPCCode, llrs: *const f32, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_batch_f32_multi(code: LDPCCode, n_parts: usize, devices: *const c_int, llrs: *const *const f32, output: *const *mut u8, iters: *const *mut u32, success: *const *mut u8, frames: *const usize, max_iters: usize, variant: c_int) -> c_int;
     pub fn labrador_ldpc_decode_ms_batch_i8_multi(code: LDPCCode, n_parts: usize, devices: *const c_int, llrs: *const *const i8, output: *const *mut u8, iters: *const *mut u32, success: *const *mut u8, frames: *const usize, max_iters: usize, variant: c_int) -> c_int;
     pub fn labrador_ldpc_decode_ms_batch_i16_multi(code: LDPCCode, n_parts: usize, devices: *const c_int, llrs: *const *const i16, output: *const *mut u8, iters: *const *mut u32, success: *const *mut u8, frames: *const usize, max_iters: usize, variant: c_int) -> c_int;
@@ -281,6 +283,38 @@ impl LDPCCode {
         }
         let o = opts.map_or(core::ptr::null(), |o| o as *const HipOpts);
         let st = unsafe { T::decode_ms_batch(self, llrs.as_ptr(), output.as_mut_ptr(), iters.as_mut_ptr(), success.as_mut_ptr(), batch, maxiters, o) };
+        if st == OK { Ok(()) } else { Err(st) }
+    }
+
+    /// Batched LAYERED decode of host f32 buffers with normalized / offset min-sum check messages
+    /// (`labrador_ldpc_decode_ms_layered_corrected_batch_f32`): every message magnitude m becomes max(scale * m - offset, 0).
+    /// `0 < scale <= 1`, `offset >= 0` in the units of the LLRs; (1, 0) is plain layered min-sum.  Buffers as [`Self::decode_ms_batch`].
+    pub fn decode_ms_layered_corrected_batch(self, llrs: &[f32], output: &mut [u8], iters: &mut [u32], success: &mut [u8], maxiters: usize, scale: f32, offset: f32, opts: Option<&HipOpts>) -> Result<(), c_int> {
+        let batch = iters.len();
+        assert_eq!(llrs.len(), batch * self.n(), "llrs.len() != batch * n");
+        assert_eq!(output.len(), batch * self.output_len(), "output.len() != batch * (n+p)/8");
+        assert_eq!(success.len(), batch, "success.len() != batch");
+        if let Some(o) = opts {
+            assert_eq!(o.memory, MEM_HOST, "slices are host memory; use the raw entry point for device buffers");
+        }
+        let o = opts.map_or(core::ptr::null(), |o| o as *const HipOpts);
+        let st = unsafe { labrador_ldpc_decode_ms_layered_corrected_batch_f32(self, llrs.as_ptr(), output.as_mut_ptr(), iters.as_mut_ptr(), success.as_mut_ptr(), batch, maxiters, scale, offset, o) };
+        if st == OK { Ok(()) } else { Err(st) }
+    }
+
+    /// [`Self::decode_ms_layered_corrected_batch`] with soft output: `app` `[batch][output_len * 8]` receives the marginals of the
+    /// returned sweep (`labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32`).
+    pub fn decode_ms_layered_corrected_soft_batch(self, llrs: &[f32], app: &mut [f32], output: &mut [u8], iters: &mut [u32], success: &mut [u8], maxiters: usize, scale: f32, offset: f32, opts: Option<&HipOpts>) -> Result<(), c_int> {
+        let batch = iters.len();
+        assert_eq!(llrs.len(), batch * self.n(), "llrs.len() != batch * n");
+        assert_eq!(app.len(), batch * self.output_len() * 8, "app.len() != batch * (n+p)");
+        assert_eq!(output.len(), batch * self.output_len(), "output.len() != batch * (n+p)/8");
+        assert_eq!(success.len(), batch, "success.len() != batch");
+        if let Some(o) = opts {
+            assert_eq!(o.memory, MEM_HOST, "slices are host memory; use the raw entry point for device buffers");
+        }
+        let o = opts.map_or(core::ptr::null(), |o| o as *const HipOpts);
+        let st = unsafe { labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32(self, llrs.as_ptr(), app.as_mut_ptr(), output.as_mut_ptr(), iters.as_mut_ptr(), success.as_mut_ptr(), batch, maxiters, scale, offset, o) };
         if st == OK { Ok(()) } else { Err(st) }
     }
 

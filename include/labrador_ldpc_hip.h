@@ -368,6 +368,31 @@ int labrador_ldpc_decode_ms_layered_soft_batch_f32(enum labrador_ldpc_code code,
                                                    uint8_t *output, uint32_t *iters, uint8_t *success,
                                                    size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
 
+/* Layered schedule with normalized / offset min-sum (f32 only).  Plain min-sum overestimates the magnitude of a check
+ * message; these calls are the two layered calls above with one step added.  Where a layer forms an edge's new message, its
+ * magnitude m (min1 or min2 of the check, capped at FLT_MAX) becomes
+ *     t  = scale * m         one IEEE f32 multiply, rounded
+ *     t  = t - offset        one IEEE f32 subtract, rounded (never fused with the multiply)
+ *     m' = t > 0 ? t : +0.0
+ * and the signs are applied to m' as they are to m.  Which of min1 / min2 an edge takes is decided on the uncorrected values;
+ * everything else (self-correction, accumulation order, LLR canonicalisation, the stop rule, iters, success, output, app,
+ * max_iters = 0) is the layered contract unchanged.
+ *   scale   0 < scale <= 1, unit-free ("normalized min-sum");
+ *   offset  0 <= offset <= FLT_MAX ("offset min-sum"), in the UNITS OF THE LLRS: a value that suits LLRs of the form +-1 + noise does
+ *           not suit the same frames scaled by 2 / sigma^2, and a value that helps one code and noise level can hurt at another.
+ * One pair per call.  A NaN, an infinity or a value outside these ranges returns LABRADOR_LDPC_HIP_EINVAL (the message names the
+ * parameter), decided with the other argument checks before any device work.  With scale = 1 and offset = 0 the step is the identity
+ * and the results equal those of the plain layered calls bit for bit, app included.  The library chooses no default: DESIGN.md 4.6
+ * gives measured starting points.  Everything else as labrador_ldpc_decode_ms_layered_batch_f32 /
+ * labrador_ldpc_decode_ms_layered_soft_batch_f32.  Returns a status code. */
+int labrador_ldpc_decode_ms_layered_corrected_batch_f32(enum labrador_ldpc_code code, const float *llrs, uint8_t *output,
+                                                        uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                        float scale, float offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32(enum labrador_ldpc_code code, const float *llrs, float *app,
+                                                             uint8_t *output, uint32_t *iters, uint8_t *success,
+                                                             size_t batch, size_t max_iters, float scale, float offset,
+                                                             const struct labrador_ldpc_hip_opts *opts);
+
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --
  * llrs[i], output[i] (8-byte aligned), iters[i], success[i], laid out as in labrador_ldpc_decode_ms_batch_* -- are DEVICE memory

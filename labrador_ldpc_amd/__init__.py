@@ -81,6 +81,9 @@ SYMBOLS = {
     **{f"labrador_ldpc_decode_ms_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f32", "i8", "i16", "i32", "f64")},
     "labrador_ldpc_decode_ms_layered_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_decode_ms_layered_soft_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
+    "labrador_ldpc_decode_ms_layered_corrected_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float, _optp]),
+    "labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float,
+                                                                        _optp]),
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -366,17 +369,26 @@ class LDPCCode(enum.IntEnum):
         return self._batch_call("labrador_ldpc_decode_ms_batch_", llrs, maxiters, output, iters, success, variant, stream, devices)
 
     def decode_ms_layered_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
-                                variant: int = 0, stream: Optional[int] = None, devices=None):
+                                variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):
         """decode_ms_batch with the block-row LAYERED schedule instead of the reference's flooding one (f32 LLRs only;
         labrador_ldpc_decode_ms_layered_batch_f32): each block row updates its checks from marginals that already
         hold the new messages of the rows before it, so a decode takes fewer sweeps and fails less often at the same cap.
         `iters` counts sweeps (0-based index of the succeeding one, maxiters on failure).  Buffers, `stream` and `devices` as
-        decode_ms_batch; `variant` 0 is the only kernel.  Returns (output, iters, success)."""
-        return self._batch_call("labrador_ldpc_decode_ms_layered_batch_", llrs, maxiters, output, iters, success, variant, stream,
-                                devices)
+        decode_ms_batch; `variant` 0 is the only kernel.  Returns (output, iters, success).
 
-    def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None):
+        `scale`, `offset`: normalized / offset min-sum (labrador_ldpc_decode_ms_layered_corrected_batch_f32) -- every
+        check message magnitude m becomes max(scale * m - offset, 0).  0 < scale <= 1; offset >= 0 is in the units of the LLRs, so
+        a value that suits one LLR scaling does not suit another.  The library checks the ranges (LdpcHipError).  The defaults are
+        plain min-sum and call the plain entry point."""
+        if scale == 1.0 and offset == 0.0:
+            return self._batch_call("labrador_ldpc_decode_ms_layered_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                    devices)
+        return self._batch_call("labrador_ldpc_decode_ms_layered_corrected_batch_", llrs, maxiters, output, iters, success, variant,
+                                stream, devices, extra=(float(scale), float(offset)))
+
+    def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=()):
         # soft: the call also writes the marginals to `app` [batch, n + p] in the dtype of `llrs`, which comes back first
+        # extra: arguments of the entry point between max_iters and opts
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
         if llrs.ndim != 2 or llrs.shape[1] != self.n():
@@ -430,7 +442,7 @@ class LDPCCode(enum.IntEnum):
         _check_result_buffer(iters, llrs, (batch,), "i32", "iters")
         _check_result_buffer(success, llrs, (batch,), "u8", "success")
         results = (app, output, iters, success) if soft else (output, iters, success)
-        _check(fn(int(self), _ptr(llrs), *(_ptr(r) for r in results), batch, maxiters, ctypes.byref(opts)))
+        _check(fn(int(self), _ptr(llrs), *(_ptr(r) for r in results), batch, maxiters, *extra, ctypes.byref(opts)))
         del keep
         return results
 
@@ -446,11 +458,15 @@ class LDPCCode(enum.IntEnum):
                                 soft=True, app=app)
 
     def decode_ms_layered_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
-                                     variant: int = 0, stream: Optional[int] = None, devices=None):
+                                     variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):
         """decode_ms_layered_batch with soft output (labrador_ldpc_decode_ms_layered_soft_batch_f32): also the marginals of the
-        returned sweep.  Buffers and return shapes as decode_ms_soft_batch: (app[batch, n + p], output, iters, success)."""
-        return self._batch_call("labrador_ldpc_decode_ms_layered_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
-                                devices, soft=True, app=app)
+        returned sweep.  Buffers and return shapes as decode_ms_soft_batch: (app[batch, n + p], output, iters, success).  `scale`
+        and `offset` as decode_ms_layered_batch (labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32)."""
+        if scale == 1.0 and offset == 0.0:
+            return self._batch_call("labrador_ldpc_decode_ms_layered_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                    devices, soft=True, app=app)
+        return self._batch_call("labrador_ldpc_decode_ms_layered_corrected_soft_batch_", llrs, maxiters, output, iters, success, variant,
+                                stream, devices, soft=True, app=app, extra=(float(scale), float(offset)))
 
     def decode_ms_batch_multi(self, parts, maxiters: int = 50, variant: int = 0):
         """Decode several device-resident batches -- one torch CUDA tensor `llrs[frames_i, n]` per part, each on its own (or the

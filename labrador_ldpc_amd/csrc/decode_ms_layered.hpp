@@ -84,10 +84,13 @@ LDPC_DEV void layered_sync()
     else LDPC_SYNC();
 }
 
-template <int CODE, bool SOFT>
+// CORRECTED: normalized / offset min-sum -- every message magnitude m becomes max(scale * m - offset, +0.0), a rounded
+// f32 multiply and a rounded f32 subtract (0 < scale <= 1, 0 <= offset <= FLT_MAX, checked by capi.hip: m is finite, so neither an
+// infinity nor a NaN can arise).  `scale` and `offset` are wave-uniform kernel arguments; without CORRECTED they are not read.
+template <int CODE, bool SOFT, bool CORRECTED = false>
 LDPC_DEV void decode_ms_layered_body(const float *__restrict__ llrs, float *__restrict__ app, uint8_t *__restrict__ output,
                                      uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out, uint32_t batch,
-                                     uint32_t maxiters, uint32_t *claim, char *lds)
+                                     uint32_t maxiters, uint32_t *claim, char *lds, float scale = 1.0f, float offset = 0.0f)
 {
     using GEO = LayeredGeometry<CODE>;
     using O = Ops<float>;
@@ -179,6 +182,8 @@ LDPC_DEV void decode_ms_layered_body(const float *__restrict__ llrs, float *__re
                         exclusive_min<O, D, true, true>(vr, e);
                         static_for<0, D>([&](auto j_) LDPC_INLINE {
                             constexpr int j = decltype(j_)::value;
+                            // which of min1 / min2 the edge takes was decided on the uncorrected |v|; t is never -0.0 or NaN
+                            if constexpr (CORRECTED) e[j] = __builtin_fmaxf(__fsub_rn(__fmul_rn(scale, e[j]), offset), 0.0f);
                             // sign product of the OTHER edges of the check: the whole product times this edge's own sign
                             nu[q][j] = __int_as_float(__float_as_int(e[j]) | ((sgn ^ __float_as_int(vr[j])) & (int)0x80000000));
                         });
@@ -282,6 +287,18 @@ decode_ms_layered_kernel(const float *__restrict__ llrs, float *__restrict__ app
 {
     __shared__ __attribute__((aligned(16))) char lds[LayeredGeometry<CODE>::LDS_BYTES];
     decode_ms_layered_body<CODE, SOFT>(llrs, app, output, iters_out, success_out, batch, maxiters, claim, lds);
+}
+
+// The same body with the correction step, under a name of its own (decode_ms_corrected_f32.hip): the plain kernels above keep
+// their symbols, their arguments and their instructions.
+template <int CODE, bool SOFT>
+__global__ void __launch_bounds__(LayeredGeometry<CODE>::WG)
+decode_ms_corrected_kernel(const float *__restrict__ llrs, float *__restrict__ app, uint8_t *__restrict__ output,
+                           uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out, uint32_t batch, uint32_t maxiters,
+                           uint32_t *claim, float scale, float offset)
+{
+    __shared__ __attribute__((aligned(16))) char lds[LayeredGeometry<CODE>::LDS_BYTES];
+    decode_ms_layered_body<CODE, SOFT, true>(llrs, app, output, iters_out, success_out, batch, maxiters, claim, lds, scale, offset);
 }
 
 }  // namespace ldpc

@@ -7,7 +7,9 @@ errors in the first k bits, until trials*k > 5e7 or errors > 5000 (:50); one CSV
 Here a trial batch runs entirely on the device: labrador_ldpc_encode_batch -> labrador_ldpc_hip_awgn_f32
 -> labrador_ldpc_decode_ms_batch_f32, errors counted with torch bit ops (plumbing).  `--schedule layered` decodes with
 labrador_ldpc_decode_ms_layered_batch_f32 instead (block-row layered schedule), so both FER curves can be drawn
-from the same frames; the default, flooding, is the reference's decoder and keeps the output unchanged.
+from the same frames; the default, flooding, is the reference's decoder and keeps the output unchanged.  `--scale` / `--offset`
+(layered schedule only) decode with normalized / offset check messages (labrador_ldpc_decode_ms_layered_corrected_batch_f32,
+DESIGN.md 4.6); `--offset` is in the units of the LLRs, which here are +-1 + noise.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -30,11 +32,15 @@ def sigma_for(code, snr_db: float, noise: str) -> float:
 
 
 def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100, batch: int = 65536,
-              max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding"):
+              max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding",
+              scale: float = 1.0, offset: float = 0.0):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
-    reference's decoder) or "layered" (decode_ms_layered_batch)."""
+    reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
+    min-sum correction (the defaults are plain min-sum); the flooding decoder has none."""
     if schedule not in ("flooding", "layered"):
         raise ValueError(f"unknown schedule {schedule!r}")
+    if schedule != "layered" and (scale != 1.0 or offset != 0.0):
+        raise ValueError("scale and offset belong to the layered schedule")
     import torch
     dev = torch.device("cuda", device)
     k8 = code.k() // 8
@@ -49,7 +55,7 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         cw = code.encode_batch(data)                                         # perftest/src/main.rs:10-12
         llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
         if schedule == "layered":
-            out, _, _ = code.decode_ms_layered_batch(llrs, maxiters)
+            out, _, _ = code.decode_ms_layered_batch(llrs, maxiters, scale=scale, offset=offset)
         else:
             out, _, _ = code.decode_ms_batch(llrs, maxiters)                # :22
         diff = out[:, :k8] ^ data                                            # :23-28
@@ -74,11 +80,16 @@ def main(argv=None):
     ap.add_argument("--max-bits", type=float, default=5e7)
     ap.add_argument("--max-errors", type=int, default=5000)
     ap.add_argument("--schedule", choices=["flooding", "layered"], default="flooding")
+    ap.add_argument("--scale", type=float, default=1.0, help="normalized min-sum factor, 0 < scale <= 1 (--schedule layered)")
+    ap.add_argument("--offset", type=float, default=0.0, help="offset min-sum term in LLR units, >= 0 (--schedule layered)")
     args = ap.parse_args(argv)
+    if args.schedule != "layered" and (args.scale != 1.0 or args.offset != 0.0):
+        ap.error("--scale and --offset need --schedule layered")
     code = LDPCCode[args.code]
     for snr in (float(x) for x in args.snrs.split(",")):
         trials, bits, errors, ber, fe = ms_trials(code, snr, args.noise, args.maxiters, args.batch,
-                                                  args.max_bits, args.max_errors, schedule=args.schedule)
+                                                  args.max_bits, args.max_errors, schedule=args.schedule,
+                                                  scale=args.scale, offset=args.offset)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 
