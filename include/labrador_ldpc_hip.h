@@ -347,7 +347,7 @@ int labrador_ldpc_decode_ms_soft_batch_f64(enum labrador_ldpc_code code, const d
                                            uint8_t *output, uint32_t *iters, uint8_t *success,
                                            size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
 
-/* Layered schedule (f32 only): block-row layered min-sum decoding instead of the reference's flooding schedule.  Block row r of the
+/* Layered schedule (f32; for i8 and i16 LLRs see the fixed-point calls further down): block-row layered min-sum decoding instead of the reference's flooding schedule.  Block row r of the
  * prototype (a "layer": 4 for the TC codes, 3 for the TM codes) updates its checks from marginals that already hold the new messages of
  * rows 0 .. r-1 of the same sweep; a sweep is one pass over every layer, and the decode stops at the first sweep whose marginals
  * satisfy every check.  Same arithmetic as decode_ms::<f32> (plain IEEE adds and subtracts, self-correction, min-sum with the FLT_MAX
@@ -392,6 +392,31 @@ int labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32(enum labrador_ldpc_
                                                              uint8_t *output, uint32_t *iters, uint8_t *success,
                                                              size_t batch, size_t max_iters, float scale, float offset,
                                                              const struct labrador_ldpc_hip_opts *opts);
+
+/* Layered schedule in fixed point (i8 and i16 LLRs): the block-row layered schedule above for quantised LLRs, with a
+ * contract of its own.  T_MAX is 127 (i8) or 32767 (i16).  An LLR is read as clamp(input, -T_MAX, T_MAX) (only the type's minimum
+ * changes).  A marginal is the LLR (0 for a punctured variable) plus the check messages of the variable's edges, summed EXACTLY in
+ * int32 (a variable has at most 6 edges, so |marginal| <= 7 * T_MAX and the order of the sum cannot matter).  Where a layer forms
+ * an edge's new variable message, nv = clamp(marginal - u, -T_MAX, T_MAX) -- the only saturation of the decoder -- followed by the
+ * self-correction of decode_ms; a check message is the exclusive minimum of the other |v| of its check (T_MAX where absent) with
+ * their sign product.  Unlike decode_ms::<i8> / ::<i16>, no single add saturates: like the f32 layered calls this is not the
+ * reference's iteration trace.
+ *   output, iters, success   as the f32 layered calls;
+ *   app         (soft form) the marginals of the returned sweep, ALWAYS int32, [batch][n + p]; all zero for max_iters = 0.
+ * Arguments, memory modes, device sets, `stream` and alignment rules as the f32 layered calls (a device `app` 16-byte aligned).
+ * `variant` 0 is the only kernel; any other value returns LABRADOR_LDPC_HIP_EUNSUPPORTED.  Returns a status code. */
+int labrador_ldpc_decode_ms_layered_fixed_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, uint8_t *output,
+                                                   uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                   const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_fixed_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, uint8_t *output,
+                                                    uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                    const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_fixed_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app,
+                                                        uint8_t *output, uint32_t *iters, uint8_t *success,
+                                                        size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_fixed_soft_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, int32_t *app,
+                                                         uint8_t *output, uint32_t *iters, uint8_t *success,
+                                                         size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
 
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --

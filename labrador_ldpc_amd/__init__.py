@@ -84,6 +84,8 @@ SYMBOLS = {
     "labrador_ldpc_decode_ms_layered_corrected_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float, _optp]),
     "labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float,
                                                                         _optp]),
+    **{f"labrador_ldpc_decode_ms_layered_fixed_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("i8", "i16")},
+    **{f"labrador_ldpc_decode_ms_layered_fixed_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -386,8 +388,28 @@ class LDPCCode(enum.IntEnum):
         return self._batch_call("labrador_ldpc_decode_ms_layered_corrected_batch_", llrs, maxiters, output, iters, success, variant,
                                 stream, devices, extra=(float(scale), float(offset)))
 
-    def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=()):
-        # soft: the call also writes the marginals to `app` [batch, n + p] in the dtype of `llrs`, which comes back first
+    def decode_ms_layered_fixed_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
+                                      variant: int = 0, stream: Optional[int] = None, devices=None):
+        """The block-row layered schedule in FIXED POINT, for int8 and int16 LLRs (labrador_ldpc_decode_ms_layered_fixed_batch_i8 /
+        _i16).  A contract of its own: marginals are exact int32 sums, the only saturation is the clamp of a new
+        variable message to +-T_MAX (127 / 32767), and an LLR equal to the type's minimum is read as -T_MAX.  `iters` counts sweeps
+        as decode_ms_layered_batch does.  Buffers, `stream` and `devices` as decode_ms_batch; `variant` 0 is the only kernel.
+        Returns (output, iters, success)."""
+        return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices)
+
+    def decode_ms_layered_fixed_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
+                                           variant: int = 0, stream: Optional[int] = None, devices=None):
+        """decode_ms_layered_fixed_batch with soft output (labrador_ldpc_decode_ms_layered_fixed_soft_batch_i8 / _i16): also the
+        marginals of the returned sweep, ALWAYS int32 whatever the LLR type.  Returns (app[batch, n + p] int32, output, iters,
+        success)."""
+        return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_soft_batch_", llrs, maxiters, output, iters, success, variant,
+                                stream, devices, soft=True, app=app, app_dtype="int32")
+
+    def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=(),
+                    app_dtype=None):
+        # soft: the call also writes the marginals to `app` [batch, n + p], which comes back first
+        # app_dtype: the dtype of `app` by name; None = the dtype of `llrs`
         # extra: arguments of the entry point between max_iters and opts
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
@@ -403,6 +425,7 @@ class LDPCCode(enum.IntEnum):
         keep = None
         if _is_torch(llrs):
             import torch
+            app_dt = llrs.dtype if app_dtype is None else getattr(torch, app_dtype)
             if not llrs.is_cuda:
                 raise ValueError("torch tensors must live on the GPU (use numpy for host buffers)")
             if not llrs.is_contiguous():
@@ -411,7 +434,7 @@ class LDPCCode(enum.IntEnum):
                 raise ValueError("device-resident buffers live on one device; `devices` is for host buffers")
             dev = llrs.device
             if soft and app is None:
-                app = torch.empty((batch, np_len), dtype=llrs.dtype, device=dev)
+                app = torch.empty((batch, np_len), dtype=app_dt, device=dev)
             if output is None:
                 output = torch.empty((batch, self.output_len()), dtype=torch.uint8, device=dev)
             if iters is None:
@@ -420,23 +443,24 @@ class LDPCCode(enum.IntEnum):
                 success = torch.empty((batch,), dtype=torch.uint8, device=dev)
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
-            if soft and (not _is_torch(app) or app.device != dev or app.dtype != llrs.dtype or tuple(app.shape) != (batch, np_len)
+            if soft and (not _is_torch(app) or app.device != dev or app.dtype != app_dt or tuple(app.shape) != (batch, np_len)
                          or not app.is_contiguous()):
-                raise ValueError(f"app must be a contiguous {llrs.dtype} tensor of shape {(batch, np_len)} on {dev}")
+                raise ValueError(f"app must be a contiguous {app_dt} tensor of shape {(batch, np_len)} on {dev}")
             opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, variant, 0, None)
         else:
             llrs = np.ascontiguousarray(llrs)
+            app_dt = llrs.dtype if app_dtype is None else np.dtype(app_dtype)
             if soft and app is None:
-                app = np.empty((batch, np_len), dtype=llrs.dtype)
+                app = np.empty((batch, np_len), dtype=app_dt)
             if output is None:
                 output = np.empty((batch, self.output_len()), dtype=np.uint8)
             if iters is None:
                 iters = np.empty((batch,), dtype=np.uint32)
             if success is None:
                 success = np.empty((batch,), dtype=np.uint8)
-            if soft and (not isinstance(app, np.ndarray) or app.dtype != llrs.dtype or app.shape != (batch, np_len)
+            if soft and (not isinstance(app, np.ndarray) or app.dtype != app_dt or app.shape != (batch, np_len)
                          or not app.flags.c_contiguous or not app.flags.writeable):
-                raise ValueError(f"app must be a writable C-contiguous {llrs.dtype} array of shape {(batch, np_len)}")
+                raise ValueError(f"app must be a writable C-contiguous {app_dt} array of shape {(batch, np_len)}")
             opts, keep = _host_opts(stream, variant, devices)
         _check_result_buffer(output, llrs, (batch, self.output_len()), "u8", "output")
         _check_result_buffer(iters, llrs, (batch,), "i32", "iters")

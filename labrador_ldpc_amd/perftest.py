@@ -9,7 +9,10 @@ Here a trial batch runs entirely on the device: labrador_ldpc_encode_batch -> la
 labrador_ldpc_decode_ms_layered_batch_f32 instead (block-row layered schedule), so both FER curves can be drawn
 from the same frames; the default, flooding, is the reference's decoder and keeps the output unchanged.  `--scale` / `--offset`
 (layered schedule only) decode with normalized / offset check messages (labrador_ldpc_decode_ms_layered_corrected_batch_f32,
-DESIGN.md 4.6); `--offset` is in the units of the LLRs, which here are +-1 + noise.
+DESIGN.md 4.6); `--offset` is in the units of the LLRs, which here are +-1 + noise.  `--llr i8` / `--llr i16` (layered schedule only)
+quantise the frames on the device -- labrador_ldpc_hip_awgn_i8's clamp(rint(`--llr-scale` * y), +-`--llr-lim`), widened for i16 --
+and decode them with the fixed-point layered decoder (labrador_ldpc_decode_ms_layered_fixed_batch_i8 / _i16); f32 is
+the default and leaves everything else as it was.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -33,14 +36,19 @@ def sigma_for(code, snr_db: float, noise: str) -> float:
 
 def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100, batch: int = 65536,
               max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding",
-              scale: float = 1.0, offset: float = 0.0):
+              scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
-    min-sum correction (the defaults are plain min-sum); the flooding decoder has none."""
+    min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
+    fixed-point layered decoder on frames quantised as clamp(rint(llr_scale * y), +-llr_lim) (layered schedule, no correction)."""
     if schedule not in ("flooding", "layered"):
         raise ValueError(f"unknown schedule {schedule!r}")
     if schedule != "layered" and (scale != 1.0 or offset != 0.0):
         raise ValueError("scale and offset belong to the layered schedule")
+    if llr not in ("f32", "i8", "i16"):
+        raise ValueError(f"unknown LLR type {llr!r}")
+    if llr != "f32" and (schedule != "layered" or scale != 1.0 or offset != 0.0):
+        raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
     import torch
     dev = torch.device("cuda", device)
     k8 = code.k() // 8
@@ -53,11 +61,15 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     while trials * code.k() <= max_bits and errors <= max_errors:
         data = torch.randint(0, 256, (batch, k8), dtype=torch.uint8, device=dev, generator=g)
         cw = code.encode_batch(data)                                         # perftest/src/main.rs:10-12
-        llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
-        if schedule == "layered":
-            out, _, _ = code.decode_ms_layered_batch(llrs, maxiters, scale=scale, offset=offset)
+        if llr != "f32":                                                     # the same noise, quantised by the i8 channel kernel
+            llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
+            out, _, _ = code.decode_ms_layered_fixed_batch(llrs if llr == "i8" else llrs.to(torch.int16), maxiters)
         else:
-            out, _, _ = code.decode_ms_batch(llrs, maxiters)                # :22
+            llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
+            if schedule == "layered":
+                out, _, _ = code.decode_ms_layered_batch(llrs, maxiters, scale=scale, offset=offset)
+            else:
+                out, _, _ = code.decode_ms_batch(llrs, maxiters)            # :22
         diff = out[:, :k8] ^ data                                            # :23-28
         per_frame = popcnt[diff.long()].sum(dim=1)
         errors += int(per_frame.sum())
@@ -82,14 +94,21 @@ def main(argv=None):
     ap.add_argument("--schedule", choices=["flooding", "layered"], default="flooding")
     ap.add_argument("--scale", type=float, default=1.0, help="normalized min-sum factor, 0 < scale <= 1 (--schedule layered)")
     ap.add_argument("--offset", type=float, default=0.0, help="offset min-sum term in LLR units, >= 0 (--schedule layered)")
+    ap.add_argument("--llr", choices=["f32", "i8", "i16"], default="f32",
+                    help="LLR type; i8 / i16: the fixed-point layered decoder on quantised frames (--schedule layered)")
+    ap.add_argument("--llr-scale", type=float, default=8.0, help="quantiser: clamp(rint(scale * y), +-lim) (--llr i8 / i16)")
+    ap.add_argument("--llr-lim", type=int, default=31, help="quantiser limit, at most 127 (--llr i8 / i16)")
     args = ap.parse_args(argv)
     if args.schedule != "layered" and (args.scale != 1.0 or args.offset != 0.0):
         ap.error("--scale and --offset need --schedule layered")
+    if args.llr != "f32" and (args.schedule != "layered" or args.scale != 1.0 or args.offset != 0.0):
+        ap.error("--llr i8 / i16 needs --schedule layered without --scale and --offset")
     code = LDPCCode[args.code]
     for snr in (float(x) for x in args.snrs.split(",")):
         trials, bits, errors, ber, fe = ms_trials(code, snr, args.noise, args.maxiters, args.batch,
                                                   args.max_bits, args.max_errors, schedule=args.schedule,
-                                                  scale=args.scale, offset=args.offset)
+                                                  scale=args.scale, offset=args.offset, llr=args.llr,
+                                                  llr_scale=args.llr_scale, llr_lim=args.llr_lim)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 
