@@ -13,6 +13,7 @@
 
 #include "decode_ms_kernel.hpp"
 #include "decode_ms_pair.hpp"
+#include "decode_ms_protos.hpp"      // launch_decode_ms, decode_ms_reads_llrs_once: declared once, for capi.hip too
 #include "decode_ms_tables.hpp"
 #include "occupancy.hpp"
 
@@ -24,26 +25,11 @@
 
 namespace ldpc {
 
-// Launch the decoder for `batch` frames on `stream`.  `variant` = 0 picks the tuned default
-// IPT (indices per thread) for the code; a positive value requests that IPT explicitly and
-// yields hipErrorInvalidConfiguration if it was not instantiated.  VARIANT_STATIC added to either
-// distributes the codewords over the workgroups by a fixed stride instead of through the launch's queue.
-// SOFT: the soft-output kernels, which also write every codeword's marginals (decoder.rs:377) to `app` [batch][n + p] in the
-// LLR type (nullptr without SOFT); hipErrorInvalidConfiguration for a `variant` whose kernel has no soft form (the header lists them).
-template <class T, bool SOFT>
-hipError_t launch_decode_ms(int code, int variant, const T *llrs, T *app, uint8_t *output, uint32_t *iters,
-                            uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
-
 // The f64 register kernels (decode_ms_f64_reg.hip, built as three objects: PART): ipt / lean select the instantiation;
 // hipErrorInvalidConfiguration if it was not built (LEAN 2, in place, has no soft form).
 template <bool SOFT, int PART = 0>
 hipError_t launch_decode_ms_f64_reg(int code, int ipt, int lean, const double *llrs, double *app, uint8_t *output, uint32_t *iters,
                                     uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
-
-// Will launch_decode_ms<T, false>(code, variant, ...) read every LLR from memory exactly once?  (false for explicit variants, which
-// are not second-guessed, and for forced two-pass NaN handling, whose second kernel reads the first one's marks.)
-template <class T>
-bool decode_ms_reads_llrs_once(int code, int variant);
 
 // Largest |LLR| for which the f32 kernels may drop the FLT_MAX clamp of the exclusive minimum
 // (decoder.rs:414-415) for a run of `maxiters` iterations.  The clamp acts only if a magnitude overflows to

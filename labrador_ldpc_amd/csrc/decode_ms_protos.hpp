@@ -1,0 +1,43 @@
+// decode_ms_protos.hpp -- the min-sum launchers that cross translation units, declared once: capi.hip calls them, the decode_ms_*.hip
+// units define them, and both sides include this header, so a signature that drifts from its definition does not compile.
+// Declarations only: capi.hip must not see the kernels (decode_ms_kernel.hpp).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+
+namespace ldpc {
+
+// Launch the decoder for `batch` frames on `stream`.  `variant` = 0 picks the tuned default
+// IPT (indices per thread) for the code; a positive value requests that IPT explicitly and
+// yields hipErrorInvalidConfiguration if it was not instantiated.  VARIANT_STATIC added to either
+// distributes the codewords over the workgroups by a fixed stride instead of through the launch's queue.
+// SOFT: the soft-output kernels, which also write every codeword's marginals (decoder.rs:377) to `app` [batch][n + p] in the
+// LLR type (nullptr without SOFT); hipErrorInvalidConfiguration for a `variant` whose kernel has no soft form (the header lists them).
+template <class T, bool SOFT>
+hipError_t launch_decode_ms(int code, int variant, const T *llrs, T *app, uint8_t *output, uint32_t *iters,
+                            uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
+
+// Will launch_decode_ms<T, false>(code, variant, ...) read every LLR from memory exactly once?  (false for explicit variants, which
+// are not second-guessed, and for forced two-pass NaN handling, whose second kernel reads the first one's marks.)
+template <class T>
+bool decode_ms_reads_llrs_once(int code, int variant);
+
+const char *decode_ms_i8_kernel_name(int code, int variant, size_t batch);      // decode_ms_i8.hip
+
+// The layered schedule (decode_ms_layered_f32.hip).  app == nullptr launches the hard form.  `variant` 0 is the only kernel of every
+// layered launcher: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).
+hipError_t launch_decode_ms_layered(int code, int variant, const float *llrs, float *app, uint8_t *output, uint32_t *iters,
+                                    uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
+// ... with normalized / offset check messages (decode_ms_corrected_f32.hip): scale and offset are the caller's, already
+// range-checked (capi.hip)
+hipError_t launch_decode_ms_layered_corrected(int code, int variant, const float *llrs, float *app, uint8_t *output, uint32_t *iters,
+                                              uint8_t *success, size_t batch, uint32_t maxiters, float scale, float offset,
+                                              hipStream_t stream);
+// ... in fixed point (decode_ms_fixed_layered.hip), T = int8_t / int16_t: the marginals are int32
+template <class T>
+hipError_t launch_decode_ms_layered_fixed(int code, int variant, const T *llrs, int32_t *app, uint8_t *output, uint32_t *iters,
+                                          uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
+
+}  // namespace ldpc

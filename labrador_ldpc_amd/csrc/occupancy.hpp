@@ -1,5 +1,5 @@
 // occupancy.hpp -- how many workgroups of a kernel the current device holds at once, for the persistent launchers
-// (decode_ms_launch.hpp, decode_ms_layered_f32.hip, decode_ms_bs.hip).
+// (decode_ms_launch.hpp, decode_ms_layered_launch.hpp, decode_ms_bs.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -11,6 +11,7 @@ import pytest
 import edge_frames
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
+from layered_helpers import layered_grid_bound, same_app, structure
 import layered_restatement as lr
 import oracle
 
@@ -30,23 +31,8 @@ def gpu():
     torch.cuda.set_device(0)
 
 
-_ST = {}
-
-
-def structure(code):
-    if code not in _ST:
-        _ST[code] = lr.Structure(int(code))
-    return _ST[code]
-
-
 def frames_per_case(code):
     return 64 if code.n() >= 5120 else 96
-
-
-def same_app(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a[~na] == b[~nb]).all())
 
 
 def check(code, llrs, maxiters, out, iters, ok, app=None, ref=None):
@@ -269,15 +255,6 @@ def test_failing_frames_at_long_caps(code):
     for m in (50, 100):
         _, it, ok, _ = layered_calls(code, llrs, m)
         assert (ok == 0).any() and (it[ok == 0] == m).all()
-
-
-def layered_grid_bound(code, cus):
-    """(most frames one round of the layered launch's persistent grid can hold, codewords per group): LayeredGeometry<CODE> (the
-    flooding default's indices per thread: 2 for TM8192, 1 otherwise), the launch's queue for workgroups of 512 threads and more."""
-    nt = code.submatrix_size() // (2 if code == LDPCCode.TM8192 else 1)
-    g = 64 // nt if nt < 64 else 1
-    wg = nt * g
-    return edge_frames.grid_bound(wg, g, wg >= 512, cus), g, wg >= 512
 
 
 @pytest.mark.parametrize("code", ALL, ids=lambda c: c.name)

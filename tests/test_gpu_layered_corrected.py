@@ -13,7 +13,7 @@ import edge_frames
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 import layered_corrected_restatement as lcr
-import layered_restatement as lr
+from layered_helpers import layered_grid_bound, same_app, structure
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -36,21 +36,6 @@ def gpu():
     if la.device_count() < 1 or not torch.cuda.is_available():
         pytest.fail("the corrected layered GPU tests need a gfx950 device")
     torch.cuda.set_device(0)
-
-
-_ST = {}
-
-
-def structure(code):
-    if code not in _ST:
-        _ST[code] = lr.Structure(int(code))
-    return _ST[code]
-
-
-def same_app(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a[~na] == b[~nb]).all())
 
 
 def check(ref, out, iters, ok, app=None):
@@ -211,14 +196,6 @@ def test_batch_sizes(code):
     for b in (1, 3, 5, 11):
         both_calls(code, llrs[:b], 25, 0.8125, 0.0)
         both_calls(code, llrs[:b], 25, 1.0, 0.1)
-
-
-def layered_grid_bound(code, cus):
-    """(most frames one round of the launch's persistent grid can hold, codewords per group, queue-fed?): LayeredGeometry<CODE>."""
-    nt = code.submatrix_size() // (2 if code == LDPCCode.TM8192 else 1)
-    g = 64 // nt if nt < 64 else 1
-    wg = nt * g
-    return edge_frames.grid_bound(wg, g, wg >= 512, cus), g, wg >= 512
 
 
 @pytest.mark.parametrize("code,pair", [(LDPCCode.TM1280, (0.8125, 0.0)), (LDPCCode.TM2048, (1.0, 0.1))], ids=["TM1280-fixed-stride", "TM2048-queue"])

@@ -13,6 +13,8 @@ import edge_frames
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 import layered_fixed_restatement as fr
+import layered_helpers
+from layered_helpers import quantise
 import oracle
 
 pytestmark = pytest.mark.gpu
@@ -34,17 +36,8 @@ def gpu():
     torch.cuda.set_device(0)
 
 
-_ST = {}
-
-
 def structure(code):
-    if code not in _ST:
-        _ST[code] = fr.Structure(int(code))
-    return _ST[code]
-
-
-def quantise(y, dtype, scale, lim):
-    return np.clip(np.rint(np.float32(scale) * y), -lim, lim).astype(dtype)
+    return layered_helpers.structure(code, fr.Structure)
 
 
 def awgn(code, rng, frames, ebn0, dtype, wide=False):

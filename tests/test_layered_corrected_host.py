@@ -15,6 +15,8 @@ import edge_frames
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 import layered_corrected_restatement as lcr
+import layered_helpers
+from layered_helpers import same_app
 import layered_restatement as lr
 import oracle
 
@@ -32,11 +34,6 @@ def corner_frames(code, rng, frames=5):
         pos = rng.choice(code.n(), size=1 + 4 * f, replace=False)
         llrs[f, pos] = rng.choice(specials, size=len(pos))
     return llrs
-
-
-def same_app(a, b):
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool((na == nb).all() and (a[~na] == b[~nb]).all())
 
 
 @pytest.mark.parametrize("code", list(LDPCCode), ids=lambda c: c.name)
@@ -196,40 +193,14 @@ def test_perftest_refuses_the_correction_with_the_flooding_schedule():
 
 @pytest.fixture(scope="module")
 def corrected_object():
-    import subprocess
-    if not os.path.exists("/opt/rocm/bin/hipcc") or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.fail("hipcc / llvm-objdump missing: the kernel-shape guards cannot run in this environment")
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "labrador_ldpc_amd", "csrc"), "-j", str(min(8, os.cpu_count() or 1))],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    obj = os.path.join(ROOT, "build", "csrc", "decode_ms_corrected_f32.o")
-    assert os.path.exists(obj)
-    return obj
+    return layered_helpers.built_object("decode_ms_corrected_f32.o")
 
 
 KERNEL = "decode_ms_corrected_kernel"
 
 
 def _kernels(obj):
-    import subprocess
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tmp = tempfile.mkdtemp()
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "--dump-section", f".hip_fatbin={tmp}/fat", obj, "/dev/null"])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={tmp}/fat",
-                           f"--output={tmp}/co", "--unbundle"])
-    dis = subprocess.check_output([f"{llvm}/llvm-objdump", "-d", f"{tmp}/co"], text=True).split("\n")
-    out, cur = {}, None
-    for line in dis:
-        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-        if m:
-            cur = m.group(1)
-            out[cur] = []
-        elif cur and "//" in line:
-            text, tail = line.split("//", 1)
-            tgt = re.search(r"<[^>]*\+0x([0-9a-f]+)>", tail)
-            out[cur].append((int(tail.split(":")[0].strip(), 16), text.strip(), int(tgt.group(1), 16) if tgt else None))
-    return {k: v for k, v in out.items() if KERNEL in k}
+    return layered_helpers.kernels(obj, KERNEL)
 
 
 def test_corrected_kernels_keep_their_sweep_loops_free_of_scratch(corrected_object):

@@ -15,6 +15,8 @@ import pytest
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 import layered_fixed_restatement as fr
+import layered_helpers
+from layered_helpers import quantise
 import layered_restatement as lr
 import oracle
 
@@ -22,10 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, OK, EUNSUPPORTED = -1, 0, -4
 TYPES = (np.int8, np.int16)
 NAMES = [f"labrador_ldpc_decode_ms_layered_fixed_{soft}batch_{t}" for soft in ("", "soft_") for t in ("i8", "i16")]
-
-
-def quantise(y, dtype, scale, lim):
-    return np.clip(np.rint(np.float32(scale) * y), -lim, lim).astype(dtype)
 
 
 def corner_frames(code, dtype, rng, noisy=3):
@@ -235,37 +233,11 @@ def test_a_variant_other_than_zero_is_unsupported_before_any_device_work():
 
 @pytest.fixture(scope="module")
 def fixed_object():
-    import subprocess
-    if not os.path.exists("/opt/rocm/bin/hipcc") or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.fail("hipcc / llvm-objdump missing: the kernel-shape guards cannot run in this environment")
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "labrador_ldpc_amd", "csrc"), "-j", str(min(8, os.cpu_count() or 1))],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    obj = os.path.join(ROOT, "build", "csrc", "decode_ms_fixed_layered.o")
-    assert os.path.exists(obj)
-    return obj
+    return layered_helpers.built_object("decode_ms_fixed_layered.o")
 
 
 def _kernels(obj):
-    import subprocess
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tmp = tempfile.mkdtemp()
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "--dump-section", f".hip_fatbin={tmp}/fat", obj, "/dev/null"])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={tmp}/fat",
-                           f"--output={tmp}/co", "--unbundle"])
-    dis = subprocess.check_output([f"{llvm}/llvm-objdump", "-d", f"{tmp}/co"], text=True).split("\n")
-    out, cur = {}, None
-    for line in dis:
-        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-        if m:
-            cur = m.group(1)
-            out[cur] = []
-        elif cur and "//" in line:
-            text, tail = line.split("//", 1)
-            tgt = re.search(r"<[^>]*\+0x([0-9a-f]+)>", tail)
-            out[cur].append((int(tail.split(":")[0].strip(), 16), text.strip(), int(tgt.group(1), 16) if tgt else None))
-    return {k: v for k, v in out.items() if "decode_ms_layered_fixed_kernel" in k}
+    return layered_helpers.kernels(obj, "decode_ms_layered_fixed_kernel")
 
 
 def test_fixed_layered_kernels_keep_their_sweep_loops_free_of_scratch(fixed_object):

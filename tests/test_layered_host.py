@@ -14,6 +14,7 @@ import pytest
 import edge_frames
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
+import layered_helpers
 import layered_restatement as lr
 import oracle
 
@@ -163,37 +164,11 @@ def test_python_binding_checks_its_buffers():
 
 @pytest.fixture(scope="module")
 def layered_object():
-    import subprocess
-    if not os.path.exists("/opt/rocm/bin/hipcc") or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        pytest.fail("hipcc / llvm-objdump missing: the kernel-shape guards cannot run in this environment")
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "labrador_ldpc_amd", "csrc"), "-j", str(min(8, os.cpu_count() or 1))],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    obj = os.path.join(ROOT, "build", "csrc", "decode_ms_layered_f32.o")
-    assert os.path.exists(obj)
-    return obj
+    return layered_helpers.built_object("decode_ms_layered_f32.o")
 
 
 def _kernels(obj):
-    import subprocess
-    import tempfile
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tmp = tempfile.mkdtemp()
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "--dump-section", f".hip_fatbin={tmp}/fat", obj, "/dev/null"])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={tmp}/fat",
-                           f"--output={tmp}/co", "--unbundle"])
-    dis = subprocess.check_output([f"{llvm}/llvm-objdump", "-d", f"{tmp}/co"], text=True).split("\n")
-    out, cur = {}, None
-    for line in dis:
-        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-        if m:
-            cur = m.group(1)
-            out[cur] = []
-        elif cur and "//" in line:
-            text, tail = line.split("//", 1)
-            tgt = re.search(r"<[^>]*\+0x([0-9a-f]+)>", tail)
-            out[cur].append((int(tail.split(":")[0].strip(), 16), text.strip(), int(tgt.group(1), 16) if tgt else None))
-    return {k: v for k, v in out.items() if "decode_ms_layered_kernel" in k}
+    return layered_helpers.kernels(obj, "decode_ms_layered_kernel")
 
 
 def test_layered_kernels_keep_their_sweep_loops_free_of_scratch(layered_object):

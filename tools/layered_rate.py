@@ -1,10 +1,23 @@
-"""Layered against flooding min-sum decoding: rate, mean passes and frame error rate of labrador_ldpc_decode_ms_layered_batch_f32 and
-labrador_ldpc_decode_ms_batch_f32 on the SAME device-resident AWGN frames (awgn_frames, f32, 25 iterations), in one process,
-alternating the two calls.
-    python tools/layered_rate.py [frames]       -> one JSON line: per case both rates (M codewords/s), mean passes, FER and the kernels
-Passes: a flooding decode that succeeds at iteration index i made i message passes (iteration 0 checks the LLRs themselves); a layered
-decode that succeeds at sweep index i made i + 1 sweeps; a failure counts as 25 either way.  Cases: TC512 3 dB, TM2048 1.7 and 2 dB,
-TM8192 2 dB.  Default 1 048 576 frames per case (TM8192: a quarter of that)."""
+"""The layered decoders next to each other and to the flooding kernels: rate, mean passes and failures of every decoder below on
+device-resident AWGN frames (cap 25), in one process, the calls alternated inside every repetition.
+    python tools/layered_rate.py [frames] [reps] [--decoders a,b,...]     -> one JSON line
+Decoders (default: all):
+    flooding_f32                                          labrador_ldpc_decode_ms_batch_f32
+    layered_f32                                           labrador_ldpc_decode_ms_layered_batch_f32
+    corrected_1_0, corrected_0.8125_0, corrected_1_0.1    labrador_ldpc_decode_ms_layered_corrected_batch_f32 at that (scale, offset): the C
+                                                          symbol itself, since the Python keywords route (1, 0) to the plain entry
+    flooding_i8                                           labrador_ldpc_decode_ms_batch_i8
+    fixed_i8, fixed_i16                                   labrador_ldpc_decode_ms_layered_fixed_batch_i8 / _i16
+The f32 frames are awgn_frames(dtype="f32"); the i8 frames are the i8 channel kernel's quantisation (8 / 31) of the same job seed, and
+the i16 frames are those widened.  Passes: a flooding decode that succeeds at iteration index i made i passes, a layered one at sweep
+index i made i + 1; a failure counts as 25.  Cases: TC512 3 dB, TM2048 1.7 and 2 dB, TM8192 2 dB.  Default 1 048 576
+frames per case (TM8192: a quarter of that) and 5 repetitions.
+Per decoder: `mcw_s` (M codewords/s, the best repetition), `mcw_s_reps`, `spread` ((max - min) / max of the repetitions: what a
+difference has to exceed), `mean_passes`, `failures`, `fer`.  Per case: `unit_equals_layered` (corrected (1, 0) makes exactly the sweeps
+of plain layered decoding, so its ratio is the price of the added instructions and kernel arguments alone), every decoder's rate
+`_over_layered_f32`, and every layered decoder's over its flooding counterpart's."""
+import argparse
+import ctypes
 import json
 import os
 import sys
@@ -16,54 +29,94 @@ import torch
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 
-FRAMES = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
-MAXITERS, REPS = 25, 3
+MAXITERS = 25
 CASES = (("TC512", 3.0), ("TM2048", 1.7), ("TM2048", 2.0), ("TM8192", 2.0))
+CORRECTED = {"corrected_1_0": (1.0, 0.0), "corrected_0.8125_0": (0.8125, 0.0), "corrected_1_0.1": (1.0, 0.1)}
+# decoder -> (its frames, its flooding counterpart; None: it is a flooding decoder)
+DECODERS = {"flooding_f32": ("f32", None), "layered_f32": ("f32", "flooding_f32"), **{k: ("f32", "flooding_f32") for k in CORRECTED},
+            "flooding_i8": ("i8", None), "fixed_i8": ("i8", "flooding_i8"), "fixed_i16": ("i16", "flooding_i8")}
+
+
+def corrected_call(code, llrs, out, it, ok, scale, offset):
+    """The corrected symbol itself (the Python keywords at (1, 0) call the plain one)."""
+    opts = la.HipOpts(llrs.device.index, la.MEM_DEVICE, torch.cuda.current_stream(llrs.device).cuda_stream, 0, 0, None)
+    st = la.lib.labrador_ldpc_decode_ms_layered_corrected_batch_f32(int(code), llrs.data_ptr(), out.data_ptr(), it.data_ptr(), ok.data_ptr(),
+                                                                    llrs.shape[0], MAXITERS, scale, offset, ctypes.byref(opts))
+    assert st == 0, la.last_error()
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("frames", nargs="?", type=int, default=1 << 20)
+    ap.add_argument("reps", nargs="?", type=int, default=5)
+    ap.add_argument("--decoders", default=",".join(DECODERS), help="comma-separated, of: " + ", ".join(DECODERS))
+    args = ap.parse_args()
+    keys = tuple(args.decoders.split(","))
+    if not keys or any(k not in DECODERS for k in keys) or len(set(keys)) != len(keys) or args.frames < 4 or args.reps < 1:
+        ap.error("bad frames, reps or --decoders")
+    pools = {}
+    for name, _ in CASES:
+        code, rng = LDPCCode[name], np.random.default_rng(1)
+        pools[name] = np.zeros((64, code.n() // 8), np.uint8)
+        for i in range(64):
+            code.copy_encode(rng.integers(0, 256, code.k() // 8, dtype=np.uint8), pools[name][i])
     dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    res = {"frames": FRAMES, "maxiters": MAXITERS, "library_build": la.lib.labrador_ldpc_hip_build_id().decode(), "cases": []}
+    torch.cuda.set_device(dev)                          # (no device: the tool ends here -- there is nothing else to time)
+    res = {"frames": args.frames, "maxiters": MAXITERS, "reps": args.reps, "decoders": list(keys),
+           "library_build": la.lib.labrador_ldpc_hip_build_id().decode(), "cases": []}
     for name, ebn0 in CASES:
         code = LDPCCode[name]
-        frames = FRAMES // 4 if code == LDPCCode.TM8192 else FRAMES
-        rng = np.random.default_rng(1)
-        pool = np.zeros((64, code.n() // 8), np.uint8)
-        for i in range(64):
-            code.copy_encode(rng.integers(0, 256, code.k() // 8, dtype=np.uint8), pool[i])
+        frames = args.frames // 4 if code == LDPCCode.TM8192 else args.frames
         sigma = float(np.sqrt(1.0 / (2.0 * (code.k() / code.n()) * 10.0 ** (ebn0 / 10.0))))
-        llrs = code.awgn_frames(torch.from_numpy(pool).to(dev), frames, sigma, seed=5, dtype="f32")
-        out = {k: torch.empty((frames, code.output_len()), dtype=torch.uint8, device=dev) for k in ("flooding", "layered")}
-        it = {k: torch.empty(frames, dtype=torch.int32, device=dev) for k in ("flooding", "layered")}
-        ok = {k: torch.empty(frames, dtype=torch.uint8, device=dev) for k in ("flooding", "layered")}
-        calls = {"flooding": lambda: code.decode_ms_batch(llrs, MAXITERS, output=out["flooding"], iters=it["flooding"], success=ok["flooding"]),
-                 "layered": lambda: code.decode_ms_layered_batch(llrs, MAXITERS, output=out["layered"], iters=it["layered"],
-                                                                 success=ok["layered"])}
+        cw = torch.from_numpy(pools[name]).to(dev)
+        llrs = {}
+        if any(DECODERS[k][0] == "f32" for k in keys):
+            llrs["f32"] = code.awgn_frames(cw, frames, sigma, seed=5, dtype="f32")
+        if any(DECODERS[k][0] != "f32" for k in keys):
+            llrs["i8"] = code.awgn_frames(cw, frames, sigma, seed=5, dtype="i8", scale=8.0, lim=31)
+            llrs["i16"] = llrs["i8"].to(torch.int16)
+        out = {k: torch.empty((frames, code.output_len()), dtype=torch.uint8, device=dev) for k in keys}
+        it = {k: torch.empty(frames, dtype=torch.int32, device=dev) for k in keys}
+        ok = {k: torch.empty(frames, dtype=torch.uint8, device=dev) for k in keys}
+
+        def call(k):
+            x = llrs[DECODERS[k][0]]
+            if k in CORRECTED:
+                return lambda: corrected_call(code, x, out[k], it[k], ok[k], *CORRECTED[k])
+            method = (code.decode_ms_batch if DECODERS[k][1] is None else
+                      code.decode_ms_layered_batch if k == "layered_f32" else code.decode_ms_layered_fixed_batch)
+            return lambda: method(x, MAXITERS, output=out[k], iters=it[k], success=ok[k])
+        calls = {k: call(k) for k in keys}
         for fn in calls.values():                       # warm-up (and the occupancy queries)
             fn()
         torch.cuda.synchronize()
-        best = {k: 1e9 for k in calls}
-        for _ in range(REPS):
+        ms = {k: [] for k in keys}
+        for _ in range(args.reps):
             for key, fn in calls.items():
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
                 fn()
                 b.record()
                 torch.cuda.synchronize()
-                best[key] = min(best[key], a.elapsed_time(b))
-        case = {"code": name, "ebn0_db": ebn0, "frames": frames,
-                "kernels": {"flooding": "decode_ms_pair_kernel" if code == LDPCCode.TM8192 else "decode_ms_kernel",
-                            "layered": "decode_ms_layered_kernel"}}
-        for key in calls:
+                ms[key].append(a.elapsed_time(b))
+        case = {"code": name, "ebn0_db": ebn0, "frames": frames}
+        if "layered_f32" in keys and "corrected_1_0" in keys:
+            case["unit_equals_layered"] = all(torch.equal(x["layered_f32"], x["corrected_1_0"]) for x in (out, it, ok))
+        for key in keys:
             succ = ok[key].to(torch.int64)
-            passes = torch.where(succ == 1, it[key].to(torch.int64) + (1 if key == "layered" else 0), torch.full_like(succ, MAXITERS))
-            case[key] = {"mcw_s": round(frames / best[key] / 1e3, 3), "ms": round(best[key], 3),
-                         "mean_passes": round(float(passes.double().mean()), 3), "fer": float(1.0 - succ.double().mean())}
-        case["layered_over_flooding"] = round(case["layered"]["mcw_s"] / case["flooding"]["mcw_s"], 4)
+            passes = torch.where(succ == 1, it[key].to(torch.int64) + (0 if DECODERS[key][1] is None else 1), torch.full_like(succ, MAXITERS))
+            rates = [frames / t / 1e3 for t in ms[key]]
+            case[key] = {"mcw_s": round(max(rates), 3), "mcw_s_reps": [round(r, 3) for r in rates],
+                         "spread": round((max(rates) - min(rates)) / max(rates), 4),
+                         "mean_passes": round(float(passes.double().mean()), 3), "failures": int((succ == 0).sum()),
+                         "fer": float(1.0 - succ.double().mean())}
+        for key in keys:
+            for base in ("layered_f32", DECODERS[key][1]):
+                if base in keys and base != key:
+                    case[f"{key}_over_{base}"] = round(case[key]["mcw_s"] / case[base]["mcw_s"], 4)
         res["cases"].append(case)
         print(json.dumps(case), file=sys.stderr, flush=True)
-        del llrs, out, it, ok
+        del llrs, out, it, ok, calls
         torch.cuda.empty_cache()
     print(json.dumps(res), flush=True)
 

@@ -5,31 +5,18 @@ or turns a per-lane select chain into branches, it emits EXEC-masked regions and
 (TM1280, round 2) to 100x (pair kernel on TM6144) slower.  A handful are legitimate (the sub-wave codeword
 handling of the TC codes, the guarded epilogue stores).
     python tools/scan_kernels.py            # table of every kernel in build/csrc/decode_ms_*.o"""
-import collections, glob, os, re, subprocess, sys, tempfile
+import glob, os, sys
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import disasm
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def scan(pattern="build/csrc/decode_ms_*.o"):
     """{(object, kernel): (instructions, exec loops)}"""
     out = {}
     for obj in sorted(glob.glob(os.path.join(ROOT, pattern))):
-        tmp = tempfile.mkdtemp()
-        subprocess.check_call([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={tmp}/fat", obj, "/dev/null"])
-        subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={tmp}/fat", f"--output={tmp}/co", "--unbundle"])
-        dis = subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", f"{tmp}/co"], text=True).split("\n")
-        cur = None
-        for l in dis:
-            m = re.match(r"^[0-9a-f]+ <(\S+)>:", l)
-            if m:
-                cur = (os.path.basename(obj), m.group(1))
-                out[cur] = [0, 0]
-                continue
-            if cur and "//" in l:
-                out[cur][0] += 1
-                if l.strip().startswith("s_cbranch_execnz"):
-                    out[cur][1] += 1
+        for kernel, body in disasm.kernels(obj).items():
+            out[(os.path.basename(obj), kernel)] = [len(body), sum(text.startswith("s_cbranch_execnz") for _, text, _ in body)]
     return out
 
 
