@@ -173,6 +173,16 @@ def _check(status: int) -> None:
 
 _NP_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.int8): "i8", np.dtype(np.int16): "i16",
               np.dtype(np.int32): "i32", np.dtype(np.float64): "f64"}
+_NP_DTYPE = {v: k for k, v in _NP_SUFFIX.items()}
+_TORCH_DTYPE: dict = {}
+
+
+def _torch_dtypes() -> dict:
+    """suffix -> torch dtype, built on first use: torch stays an optional import"""
+    if not _TORCH_DTYPE:
+        import torch
+        _TORCH_DTYPE.update(f32=torch.float32, i8=torch.int8, i16=torch.int16, i32=torch.int32, f64=torch.float64)
+    return _TORCH_DTYPE
 
 
 _DECODE_MS_FN: dict = {}
@@ -197,8 +207,7 @@ def _ptr(a) -> int:
 
 def _suffix(a) -> str:
     if _is_torch(a):
-        import torch
-        return {torch.float32: "f32", torch.int8: "i8", torch.int16: "i16", torch.int32: "i32", torch.float64: "f64"}[a.dtype]
+        return {v: k for k, v in _torch_dtypes().items()}[a.dtype]
     return _NP_SUFFIX[a.dtype]
 
 
@@ -218,6 +227,37 @@ def _host_opts(stream, variant: int, devices):
         raise ValueError("empty device list")
     arr = (ctypes.c_int * len(devs))(*devs)
     return HipOpts(DEVICE_CURRENT, MEM_HOST, None, variant, len(devs), arr), arr   # keep arr alive during the call
+
+
+def _device_opts(tensor, stream, variant: int = 0):
+    """opts for buffers resident on `tensor`'s device; `stream` None = torch's current stream of that device"""
+    import torch
+    dev = tensor.device
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    return HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, variant, 0, None)
+
+
+def _result_buffer(buf, like, shape, kind: str, name: str, exact: bool = False):
+    """The result buffer `name` of a call whose input is `like`: `buf` once it is checked, or, for None, a new one where `like`
+    lives (a torch tensor's device, or the host as a numpy array).  kind: a dtype suffix.  exact=False is for the decoders' u8 and
+    i32 outputs (_check_result_buffer; a new numpy `iters` is uint32); exact=True for a buffer in a dtype the caller chose."""
+    torch_like = _is_torch(like)
+    if torch_like:
+        import torch
+        dt = torch.uint8 if kind == "u8" else _torch_dtypes()[kind]
+    else:
+        dt = _NP_DTYPE[kind] if exact else np.dtype({"u8": np.uint8, "i32": np.uint32}[kind])
+    if buf is None:
+        return torch.empty(shape, dtype=dt, device=like.device) if torch_like else np.empty(shape, dtype=dt)
+    if not exact:
+        _check_result_buffer(buf, like, shape, kind, name)
+    elif torch_like:
+        if not (_is_torch(buf) and buf.device == like.device and buf.dtype == dt and tuple(buf.shape) == shape and buf.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {like.device}")
+    elif not (isinstance(buf, np.ndarray) and buf.dtype == dt and buf.shape == shape and buf.flags.c_contiguous and buf.flags.writeable):
+        raise ValueError(f"{name} must be a writable C-contiguous {dt} array of shape {shape}")
+    return buf
 
 
 def _check_result_buffer(buf, like, shape, kinds, name: str):
@@ -404,12 +444,12 @@ class LDPCCode(enum.IntEnum):
         marginals of the returned sweep, ALWAYS int32 whatever the LLR type.  Returns (app[batch, n + p] int32, output, iters,
         success)."""
         return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_soft_batch_", llrs, maxiters, output, iters, success, variant,
-                                stream, devices, soft=True, app=app, app_dtype="int32")
+                                stream, devices, soft=True, app=app, app_dtype="i32")
 
     def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=(),
                     app_dtype=None):
         # soft: the call also writes the marginals to `app` [batch, n + p], which comes back first
-        # app_dtype: the dtype of `app` by name; None = the dtype of `llrs`
+        # app_dtype: the dtype of `app` as a suffix ("i32"); None = the dtype of `llrs`
         # extra: arguments of the entry point between max_iters and opts
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
@@ -424,47 +464,22 @@ class LDPCCode(enum.IntEnum):
             raise LdpcHipError(f"no batched kernel for dtype {llrs.dtype}")
         keep = None
         if _is_torch(llrs):
-            import torch
-            app_dt = llrs.dtype if app_dtype is None else getattr(torch, app_dtype)
             if not llrs.is_cuda:
                 raise ValueError("torch tensors must live on the GPU (use numpy for host buffers)")
             if not llrs.is_contiguous():
                 raise ValueError("llrs must be contiguous")
             if devices is not None:
                 raise ValueError("device-resident buffers live on one device; `devices` is for host buffers")
-            dev = llrs.device
-            if soft and app is None:
-                app = torch.empty((batch, np_len), dtype=app_dt, device=dev)
-            if output is None:
-                output = torch.empty((batch, self.output_len()), dtype=torch.uint8, device=dev)
-            if iters is None:
-                iters = torch.empty((batch,), dtype=torch.int32, device=dev)
-            if success is None:
-                success = torch.empty((batch,), dtype=torch.uint8, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            if soft and (not _is_torch(app) or app.device != dev or app.dtype != app_dt or tuple(app.shape) != (batch, np_len)
-                         or not app.is_contiguous()):
-                raise ValueError(f"app must be a contiguous {app_dt} tensor of shape {(batch, np_len)} on {dev}")
-            opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, variant, 0, None)
+            opts = _device_opts(llrs, stream, variant)
         else:
             llrs = np.ascontiguousarray(llrs)
-            app_dt = llrs.dtype if app_dtype is None else np.dtype(app_dtype)
-            if soft and app is None:
-                app = np.empty((batch, np_len), dtype=app_dt)
-            if output is None:
-                output = np.empty((batch, self.output_len()), dtype=np.uint8)
-            if iters is None:
-                iters = np.empty((batch,), dtype=np.uint32)
-            if success is None:
-                success = np.empty((batch,), dtype=np.uint8)
-            if soft and (not isinstance(app, np.ndarray) or app.dtype != app_dt or app.shape != (batch, np_len)
-                         or not app.flags.c_contiguous or not app.flags.writeable):
-                raise ValueError(f"app must be a writable C-contiguous {app_dt} array of shape {(batch, np_len)}")
+        if soft:
+            app = _result_buffer(app, llrs, (batch, np_len), app_dtype or _suffix(llrs), "app", exact=True)
+        if not _is_torch(llrs):
             opts, keep = _host_opts(stream, variant, devices)
-        _check_result_buffer(output, llrs, (batch, self.output_len()), "u8", "output")
-        _check_result_buffer(iters, llrs, (batch,), "i32", "iters")
-        _check_result_buffer(success, llrs, (batch,), "u8", "success")
+        output = _result_buffer(output, llrs, (batch, self.output_len()), "u8", "output")
+        iters = _result_buffer(iters, llrs, (batch,), "i32", "iters")
+        success = _result_buffer(success, llrs, (batch,), "u8", "success")
         results = (app, output, iters, success) if soft else (output, iters, success)
         _check(fn(int(self), _ptr(llrs), *(_ptr(r) for r in results), batch, maxiters, *extra, ctypes.byref(opts)))
         del keep
@@ -548,19 +563,13 @@ class LDPCCode(enum.IntEnum):
             import torch
             if not (input.is_cuda and input.dtype == torch.uint8 and input.is_contiguous()):
                 raise ValueError("input must be a contiguous uint8 CUDA tensor")
-            dev = input.device
-            output = torch.empty((batch, self.output_len()), dtype=torch.uint8, device=dev)
-            iters = torch.empty((batch,), dtype=torch.int32, device=dev)
-            success = torch.empty((batch,), dtype=torch.uint8, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, 0, 0, None)
+            opts = _device_opts(input, stream)
         else:
             input = np.ascontiguousarray(input, dtype=np.uint8)
-            output = np.empty((batch, self.output_len()), dtype=np.uint8)
-            iters = np.empty((batch,), dtype=np.uint32)
-            success = np.empty((batch,), dtype=np.uint8)
             opts, _keep = _host_opts(stream, 0, devices)
+        output = _result_buffer(None, input, (batch, self.output_len()), "u8", "output")
+        iters = _result_buffer(None, input, (batch,), "i32", "iters")
+        success = _result_buffer(None, input, (batch,), "u8", "success")
         _check(lib.labrador_ldpc_decode_bf_batch(int(self), _ptr(input), _ptr(output), _ptr(iters), _ptr(success),
                                                  batch, maxiters, ctypes.byref(opts)))
         return output, iters, success
@@ -575,18 +584,11 @@ class LDPCCode(enum.IntEnum):
             import torch
             if not (data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous()):
                 raise ValueError("data must be a contiguous uint8 CUDA tensor")
-            dev = data.device
-            if codewords is None:
-                codewords = torch.empty((batch, self.n() // 8), dtype=torch.uint8, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, 0, 0, None)
+            opts = _device_opts(data, stream)
         else:
             data = np.ascontiguousarray(data, dtype=np.uint8)
-            if codewords is None:
-                codewords = np.empty((batch, self.n() // 8), dtype=np.uint8)
             opts, _keep = _host_opts(stream, 0, devices)
-        _check_result_buffer(codewords, data, (batch, self.n() // 8), "u8", "codewords")
+        codewords = _result_buffer(codewords, data, (batch, self.n() // 8), "u8", "codewords")
         _check(lib.labrador_ldpc_encode_batch(int(self), _ptr(data), _ptr(codewords), batch, ctypes.byref(opts)))
         return codewords
 
@@ -597,29 +599,17 @@ class LDPCCode(enum.IntEnum):
         if input.ndim != 2 or input.shape[1] != self.n() // 8:
             raise ValueError("input must be [batch, n/8]")
         batch = input.shape[0]
+        if dtype not in _NP_DTYPE:
+            raise KeyError(dtype)
         if _is_torch(input):
             import torch
-            tdt = {"f32": torch.float32, "i8": torch.int8, "i16": torch.int16, "i32": torch.int32, "f64": torch.float64}[dtype]
             if not (input.is_cuda and input.dtype == torch.uint8 and input.is_contiguous()):
                 raise ValueError("input must be a contiguous uint8 CUDA tensor")
-            dev = input.device
-            if llrs is None:
-                llrs = torch.empty((batch, self.n()), dtype=tdt, device=dev)
-            elif not (_is_torch(llrs) and llrs.device == dev and llrs.dtype == tdt and tuple(llrs.shape) == (batch, self.n())
-                      and llrs.is_contiguous()):
-                raise ValueError(f"llrs must be a contiguous {tdt} tensor of shape ({batch}, {self.n()}) on {dev}")
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, 0, 0, None)
+            opts = _device_opts(input, stream)
         else:
-            ndt = {v: k for k, v in _NP_SUFFIX.items()}[dtype]
             input = np.ascontiguousarray(input, dtype=np.uint8)
-            if llrs is None:
-                llrs = np.empty((batch, self.n()), dtype=ndt)
-            elif not (isinstance(llrs, np.ndarray) and llrs.dtype == ndt and llrs.shape == (batch, self.n())
-                      and llrs.flags.c_contiguous and llrs.flags.writeable):
-                raise ValueError(f"llrs must be a writable C-contiguous {ndt} array of shape ({batch}, {self.n()})")
             opts = HipOpts(DEVICE_CURRENT, MEM_HOST, None, 0, 0, None)
+        llrs = _result_buffer(llrs, input, (batch, self.n()), dtype, "llrs", exact=True)
         _check(getattr(lib, "labrador_ldpc_hard_to_llrs_batch_" + dtype)(int(self), _ptr(input), _ptr(llrs), batch, ctypes.byref(opts)))
         return llrs
 
@@ -629,23 +619,15 @@ class LDPCCode(enum.IntEnum):
             raise ValueError("llrs must be [batch, n]")
         batch = llrs.shape[0]
         if _is_torch(llrs):
-            import torch
             if not (llrs.is_cuda and llrs.is_contiguous()):
                 raise ValueError("llrs must be a contiguous CUDA tensor")
-            dev = llrs.device
-            if output is None:
-                output = torch.empty((batch, self.n() // 8), dtype=torch.uint8, device=dev)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, 0, 0, None)
+            opts = _device_opts(llrs, stream)
         else:
             if llrs.dtype not in _NP_SUFFIX:
                 raise ValueError("llrs dtype must be one of int8, int16, int32, float32, float64")
             llrs = np.ascontiguousarray(llrs)
-            if output is None:
-                output = np.empty((batch, self.n() // 8), dtype=np.uint8)
             opts = HipOpts(DEVICE_CURRENT, MEM_HOST, None, 0, 0, None)
-        _check_result_buffer(output, llrs, (batch, self.n() // 8), "u8", "output")
+        output = _result_buffer(output, llrs, (batch, self.n() // 8), "u8", "output")
         _check(getattr(lib, "labrador_ldpc_llrs_to_hard_batch_" + _suffix(llrs))(int(self), _ptr(llrs), _ptr(output), batch, ctypes.byref(opts)))
         return output
 
@@ -659,16 +641,10 @@ class LDPCCode(enum.IntEnum):
         import torch
         if not (codewords.is_cuda and codewords.dtype == torch.uint8 and codewords.is_contiguous()):
             raise ValueError("codewords must be a contiguous uint8 CUDA tensor [pool, n/8]")
-        dev = codewords.device
-        tdt = {"f32": torch.float32, "i8": torch.int8}[dtype]
-        if out is None:
-            out = torch.empty((batch, self.n()), dtype=tdt, device=dev)
-        elif not (_is_torch(out) and out.device == dev and out.dtype == tdt and tuple(out.shape) == (batch, self.n())
-                  and out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous {tdt} tensor of shape ({batch}, {self.n()}) on {dev}")
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        opts = HipOpts(dev.index if dev.index is not None else -1, MEM_DEVICE, stream, 0, 0, None)
+        if dtype not in ("f32", "i8"):
+            raise KeyError(dtype)
+        out = _result_buffer(out, codewords, (batch, self.n()), dtype, "out", exact=True)
+        opts = _device_opts(codewords, stream)
         if dtype == "f32":
             _check(lib.labrador_ldpc_hip_awgn_f32_at(int(self), codewords.data_ptr(), codewords.shape[0],
                                                      out.data_ptr(), first_frame, batch, sigma, seed, ctypes.byref(opts)))

@@ -15,6 +15,7 @@
 #include "decode_ms_pair.hpp"
 #include "decode_ms_protos.hpp"      // launch_decode_ms, decode_ms_reads_llrs_once: declared once, for capi.hip too
 #include "decode_ms_tables.hpp"
+#include "env_flag.hpp"
 #include "occupancy.hpp"
 
 // LDPC_SOFT=1 (Makefile: the decode_ms_soft_*.o objects): the translation unit instantiates the soft-output forms of its kernels,
@@ -68,7 +69,7 @@ constexpr unsigned LF_STATIC = 1, LF_ONE_PASS = 2, LF_TWO_PASS = 4;
 // the word cannot be allocated.
 inline uint32_t *claim_counter(hipStream_t stream)
 {
-    static const bool off = [] { const char *e = std::getenv("LABRADOR_LDPC_HIP_STATIC"); return e && *e && *e != '0'; }();
+    static const bool off = env_flag("LABRADOR_LDPC_HIP_STATIC");
     if (off || stream == hipStreamPerThread) return nullptr;
     if (stream != nullptr) {                     // (the legacy stream cannot be captured; asking would disturb a global-mode capture)
         hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

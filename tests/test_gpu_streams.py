@@ -34,7 +34,7 @@ def test_non_default_stream_is_honoured():
 
 
 def test_host_batch_larger_than_one_staging_chunk():
-    """MEM_HOST calls stage at most 262 144 frames at a time (csrc/capi.hip chunk_items)."""
+    """MEM_HOST calls stage at most 262 144 frames at a time (csrc/capi_staging.hpp chunk_items)."""
     code = LDPCCode.TC128
     rng = np.random.default_rng(2)
     base, _ = oracle.awgn_llrs(code, rng, 1024, 3.0, np.float32)
