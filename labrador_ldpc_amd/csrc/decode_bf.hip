@@ -20,7 +20,7 @@
 #include <cstdlib>
 
 #include "decode_bf.hpp"
-#include "decode_ms_kernel.hpp"      // static_for, pi_dev, prototype helpers
+#include "decode_ms_util.hpp"        // static_for, pi_dev, prototype helpers
 
 namespace ldpc {
 

@@ -7,8 +7,7 @@
 #include <cfloat>
 #include <cstdint>
 
-#include "decode_ms_kernel.hpp"      // static_for, prototype helpers, phi/theta accessors
-#include "decode_ms_launch.hpp"
+#include "decode_ms_launch.hpp"      // the f64 register kernels' launcher; static_for, prototype helpers, phi/theta accessors
 
 namespace ldpc {
 

@@ -34,20 +34,15 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
-#include <cfloat>
 #include <cstdint>
 #include <type_traits>
 
 #include "codes.hpp"
 #include "notify.hpp"
 
-#define LDPC_INLINE __attribute__((always_inline))
-
+#include "decode_ms_ops.hpp"       // Ops<T>, exclusive_min (the v_min3_f32 trees), soft_value; through it decode_ms_util.hpp: static_for, prototype analysis, pi_dev, LDPC_SYNC
 #include "decode_ms_tuning.hpp"    // tuned settings (kernel experiments and timing diagnostics: tools/kbench/)
 
-// Workgroup barrier for LDS hand-offs.  Written out (instead of __syncthreads()) so that it waits
-// for LDS operations only and not for the asynchronous LLR staging copies counted in vmcnt.
-#define LDPC_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #if LDPC_PRIO == 1
 #define LDPC_SETPRIO(n) do { if constexpr (PRIO_WAVES) { __builtin_amdgcn_s_setprio(n); __builtin_amdgcn_sched_barrier(0); } } while (0)
 #elif LDPC_PRIO == 2
@@ -55,533 +50,8 @@
 #else
 #define LDPC_SETPRIO(n) do { } while (0)
 #endif
-#define LDPC_DEV __device__ __forceinline__
 
 namespace ldpc {
-
-// ---- compile-time loop ------------------------------------------------------------------
-template <int N> struct IC { static constexpr int value = N; constexpr operator int() const { return N; } };
-template <int B, int E, class F>
-LDPC_DEV void static_for(F &&f)
-{
-    if constexpr (B < E) { f(IC<B>{}); static_for<B + 1, E>(f); }
-}
-
-// XOR of D words with three-input XORs (v_bitop3_b32 issues at the fast VALU rate on gfx950)
-template <int D>
-LDPC_DEV int xor_reduce(const int (&w)[D])
-{
-    int acc = w[0];
-    static_for<0, (D - 1) / 2>([&](auto I_) LDPC_INLINE {
-        constexpr int i = 1 + 2 * decltype(I_)::value;
-        acc = __builtin_amdgcn_bitop3_b32(acc, w[i], w[i + 1], 0x96);
-    });
-    if constexpr (D % 2 == 0) acc ^= w[D - 1];
-    return acc;
-}
-
-// acc ^ w[0] ^ ... ^ w[N - 1], two words per v_bitop3_b32 (a running `acc ^= w` costs one v_xor per word)
-template <int N, int D>
-LDPC_DEV int xor_into(int acc, const int (&w)[D])
-{
-    static_assert(N <= D);
-    static_for<0, N / 2>([&](auto I_) LDPC_INLINE {
-        constexpr int i = 2 * decltype(I_)::value;
-        acc = __builtin_amdgcn_bitop3_b32(acc, w[i], w[i + 1], 0x96);
-    });
-    if constexpr (N % 2 == 1) acc ^= w[N - 1];
-    return acc;
-}
-
-// ---- prototype analysis -------------------------------------------------------------------
-constexpr bool blk_local(const Block &b) { return b.kind == BLK_I && b.val == 0; }
-constexpr int count_exchanged(const Prototype &p)
-{
-    int c = 0;
-    for (int b = 0; b < p.n_blocks; ++b) c += blk_local(p.blk[b]) ? 0 : 1;
-    return c;
-}
-// slot of block b among the exchanged (non-local) blocks, -1 if local
-constexpr int exch_slot(const Prototype &p, int b)
-{
-    if (blk_local(p.blk[b])) return -1;
-    int c = 0;
-    for (int i = 0; i < b; ++i) c += blk_local(p.blk[i]) ? 0 : 1;
-    return c;
-}
-constexpr bool col_exchanged(const Prototype &p, int col)
-{
-    for (int b = 0; b < p.n_blocks; ++b)
-        if (p.blk[b].col == col && !blk_local(p.blk[b])) return true;
-    return false;
-}
-constexpr int count_exch_cols(const Prototype &p)
-{
-    int c = 0;
-    for (int col = 0; col < p.n_cols; ++col) c += col_exchanged(p, col) ? 1 : 0;
-    return c;
-}
-// slot of block column `col` among the columns whose marginals are exchanged, -1 if none
-constexpr int col_slot(const Prototype &p, int col)
-{
-    if (!col_exchanged(p, col)) return -1;
-    int c = 0;
-    for (int i = 0; i < col; ++i) c += col_exchanged(p, i) ? 1 : 0;
-    return c;
-}
-constexpr int row_degree(const Prototype &p, int row)
-{
-    int c = 0;
-    for (int b = 0; b < p.n_blocks; ++b) c += p.blk[b].row == row ? 1 : 0;
-    return c;
-}
-// block index of the j-th block of block row `row`
-constexpr int row_block(const Prototype &p, int row, int j)
-{
-    for (int b = 0; b < p.n_blocks; ++b)
-        if (p.blk[b].row == row && j-- == 0) return b;
-    return -1;
-}
-
-// ---- arithmetic per LLR type: DecodeFrom, decoder.rs:22-86 ----------------------------------
-// Register values are kept so that "negative" (hard_bit, decoder.rs:49/:76) is exactly bit 31
-// of the 32-bit pattern: true for two's-complement ints, and true for floats because no
-// value in this kernel is ever -0.0 (LLRs are canonicalised with +0.0 on load; sums and
-// differences of such values cannot produce -0.0; see DESIGN.md "signed zeros").
-template <class T> struct Ops;
-
-template <> struct Ops<float> {                       // decoder.rs:69-77
-    using R = float;                                   // register type
-    using E = float;                                   // LDS exchange element type
-    LDPC_DEV static R zero() { return 0.0f; }
-    LDPC_DEV static R maxval() { return FLT_MAX; }                              // :72
-    // -0.0 -> +0.0, and every NaN -> +inf.
-    // NaN LLRs: the reference's hard_bit is `x < 0.0` (:76), false for a NaN whatever its sign bit, while this kernel reads
-    // "negative" from bit 31, so a sign-carrying NaN must not reach the registers.  Clearing that bit on the common path
-    // (compare + select, integer bit tricks, an asm bundle, a ballot and a cold fix-up branch: all tried) cost the kernels at
-    // their register limit 20-50 spilled registers.  But a NaN LLR and a +inf LLR are THE SAME INPUT to decode_ms -- every
-    // output bit, the iteration count and the success flag agree:
-    //   * the marginal is NaN + u resp. inf + u, for ever (u is finite: +-min1 / min2 <= maxval, :391-405): never `< 0`, so
-    //     hard bit 0 (:457, :469) and no contribution to the parity (:445);
-    //   * every message along the variable's edges is NaN - u resp. inf - u = the same again; it is kept by the
-    //     self-correction (old v is 0, then itself: `hard_bit() ==` holds, :422), is never `< 0` (no sign contribution, :439),
-    //     and its magnitude NaN resp. inf passes neither `< min1` nor `< min2` (:430, :433) nor `== min1` (:391): the checks
-    //     see an edge that takes no part in the minima, and its own u is min1 either way.
-    // So the load maps NaN to +inf with one v_min_f32 -- minNum(NaN, inf) = inf; the add before it quiets a signalling NaN,
-    // which minNum would otherwise turn into a quiet NaN.  +inf LLRs were always part of the contract (tests since round 1).
-    // (Written with the builtin, not as inline asm: an asm statement between a load and its use makes the compiler wait
-    // for every LLR load on the spot -- ten serialised L2 round trips per variable phase in the register-lean kernel.)
-    LDPC_DEV static R load(float x) { return __builtin_fminf(x + 0.0f, __builtin_inff()); }
-    // LATE canonicalisation, for the kernels where the load-time form does not come for free.  Without the NaN mapping the
-    // compiler never materialised `llr = raw + 0.0`: it kept the raw registers and folded the `+ 0.0` into the copy that starts
-    // each marginal's accumulation.  A two-operation load() cannot be folded that way; it becomes a second set of values, and
-    // the two kernels that sit at a forced register limit (TM1280 f32 at 168, the register-lean TM5120 f32 at 128) spilled
-    // 20-45 more registers for it (-17 % / -16 %, profiles/r03_kbench/kb4.txt).  Those kernels keep the RAW LLR (keep_raw), add
-    // it as it is, and canonicalise the finished marginal instead: raw + u1 + ... equals llr + u1 + ... as a VALUE at every
-    // step (a -0.0 addend behaves like +0.0 unless everything is -0.0), `+ 0.0` then turns a -0.0 result into +0.0, and a NaN
-    // LLR leaves a NaN marginal, which min(., inf) maps to the +inf marginal a +inf LLR would have left.  One more v_min per
-    // transmitted column and iteration, no extra registers.
-    LDPC_DEV static R canon_late(R x) { return __builtin_fminf(x + 0.0f, __builtin_inff()); }
-    LDPC_DEV static R keep_raw(float x) { return x; }
-    LDPC_DEV static R load_nonan(float x) { return x + 0.0f; }                   // for values a vote has shown to hold no NaN
-    LDPC_DEV static float store(R x) { return x; }
-    LDPC_DEV static R from_lds(float x) { return x; }                           // already canonical
-    LDPC_DEV static int bits(R x) { return __float_as_int(x); }
-    static constexpr bool SIGN_WORD_IS_BIT31_ONLY = true;      // (the register-lean check phases form it from raw bits themselves)
-    LDPC_DEV static int sign_word(R x) { return __float_as_int(x) & (int)0x80000000; }     // bit 31 of a message, alone
-    LDPC_DEV static R add(R a, R b) { return a + b; }                           // :74
-    LDPC_DEV static R sub(R a, R b) { return a - b; }                           // :75
-    LDPC_DEV static R sub_nv(R a, R b) { return a - b; }                        // the new v of an edge (:421)
-    LDPC_DEV static R mag(R x) { return __builtin_fabsf(x); }                   // :73 (may be +inf)
-    // min of magnitudes.  AX/AY/AZ say whether the operand is a signed message whose magnitude is
-    // meant (the |x| source modifier is free) or already a magnitude.  Written as asm so that the
-    // operation tree of exclusive_min() is emitted as designed: through fminf() LLVM re-associates
-    // it into ~50 % more v_min ops plus canonicalising v_max ops.
-    template <bool AX, bool AY>
-    LDPC_DEV static R min2(R x, R y)
-    {
-        R d;
-        if constexpr (AX && AY) asm("v_min_f32_e64 %0, |%1|, |%2|" : "=v"(d) : "v"(x), "v"(y));
-        else if constexpr (AX) asm("v_min_f32_e64 %0, |%1|, %2" : "=v"(d) : "v"(x), "v"(y));
-        else if constexpr (AY) asm("v_min_f32_e64 %0, %1, |%2|" : "=v"(d) : "v"(x), "v"(y));
-        else asm("v_min_f32_e32 %0, %1, %2" : "=v"(d) : "v"(x), "v"(y));
-        return d;
-    }
-    // min(maxval, ...): the cap comes from an SGPR
-    template <bool AX>
-    LDPC_DEV static R min2_cap(R x)
-    {
-        R d;
-        const float cap = FLT_MAX;
-        if constexpr (AX) asm("v_min_f32_e64 %0, |%1|, %2" : "=v"(d) : "v"(x), "s"(cap));
-        else asm("v_min_f32_e32 %0, %2, %1" : "=v"(d) : "v"(x), "s"(cap));
-        return d;
-    }
-    template <bool AX, bool AY>
-    LDPC_DEV static R min3_cap(R x, R y)
-    {
-        R d;
-        const float cap = FLT_MAX;
-        if constexpr (AX && AY) asm("v_min3_f32 %0, |%1|, |%2|, %3" : "=v"(d) : "v"(x), "v"(y), "s"(cap));
-        else if constexpr (!AX && !AY) asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "s"(cap));
-        else d = min2_cap<false>(min2<AX, AY>(x, y));
-        return d;
-    }
-    template <bool AX, bool AY, bool AZ>
-    LDPC_DEV static R min3(R x, R y, R z)
-    {
-        R d;
-        if constexpr (AX && AY && AZ) asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(d) : "v"(x), "v"(y), "v"(z));
-        else if constexpr (AX && AY) asm("v_min3_f32 %0, |%1|, |%2|, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
-        else if constexpr (!AX && !AY && !AZ) asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
-        else d = min2<false, AZ>(min2<AX, AY>(x, y), z);
-        return d;
-    }
-    // magnitude `m` (>= 0) with the sign taken from bit 31 of `s`
-    LDPC_DEV static R with_sign(R m, int s)
-    {
-        return __int_as_float((__float_as_int(m) & 0x7FFFFFFF) | (s & (int)0x80000000));
-    }
-    LDPC_DEV static R select_zero(bool z, R x) { return z ? 0.0f : x; }
-    // x where p is not a negative non-zero number, else +0: "bits(p) <= 0x80000000" as the borrow of an integer
-    // subtraction (an I-class VOP2 operation that pairs with the F and I classes) instead of a float compare (C class)
-    LDPC_DEV static R keep_unless_negative(R p, R x)
-    {
-        // (the same through __builtin_usub_overflow, which lets the compiler place the wait states, measures within
-        // +-1 % of this bundle on every kernel)
-        R r;
-        asm("v_subrev_co_u32_e32 %0, vcc, %2, %1\n\ts_nop 1\n\tv_cndmask_b32_e32 %0, 0, %3, vcc"
-            : "=&v"(r) : "v"(p), "s"(0x80000001u), "v"(x) : "vcc");
-        return r;
-    }
-    // Self-correction test of decoder.rs:422: drop nv iff old != 0 and sign(nv) != sign(old).
-    // `old` with its sign flipped when nv is negative is a negative NON-ZERO float exactly then
-    // (old is never -0.0), so one three-input bit op (old ^ (nv & 0x80000000)) and one float
-    // compare decide it; "-0.0 < 0" is false, which is the old == 0 case.  (A NaN nv -- always the positive quiet
-    // one, see load() -- leaves t = old: dropped iff old < 0, kept otherwise, as `NaN.hard_bit() == old.hard_bit()`.)
-    LDPC_DEV static bool drop(R nv, R old)
-    {
-        const int t = __builtin_amdgcn_bitop3_b32(__float_as_int(old), __float_as_int(nv), (int)0x80000000, 0x78);
-        return __int_as_float(t) < 0.0f;
-    }
-    // Self-correction as a CLAMP (FORM 2 / 3 / 5).  "Keep nv iff it lies on old's side of zero (any side if old == 0)" is
-    // v = median(nv, 0, X) for any X with X = nv when old == 0 and, when old != 0, the sign of old and |X| >= |nv|.
-    //   FORM 2:  X = fma(old, big, nv)   (one v_fma_f32: full rate on gfx950, tools/ubench/valu_rate.hip) -- needs
-    //            big * |old| > |nv| for every nonzero old and every nv of the decode, which the caller guarantees (integer
-    //            messages: big = 2^20; f32: the tightened range vote, nocap_limit_for());
-    //   FORM 3:  X = nv + mul_legacy(old, inf): +-inf for every nonzero old (denormals included), 0 * inf = 0 under
-    //            the legacy rule, so no range condition beyond "nothing is NaN or infinite";
-    //   FORM 5:  the same decision without a median: three full-rate operations, none of the 4-cycle class.
-    // One v_med3_f32 replaces the compare and the select of forms 0 / 1, and with them the VCC round trip between the two
-    // (two wait states on gfx950): sub, fma, med3 instead of sub, mul, cmp, cndmask.  Per edge update 0.94 ns against
-    // 1.13-1.25 ns per instruction slot in the micro-benchmark (profiles/r03_final/valu_rate.txt).
-    template <int FORM>
-    LDPC_DEV static R clamp_to_side(R nv, R old, float big)
-    {
-        static_assert(FORM == 2 || FORM == 3 || FORM == 5, "clamp forms of the self-correction: 2, 3, 5 (6: integer messages only, IntOps)");
-        R x, r;
-        if constexpr (FORM == 2) {
-            asm("v_fma_f32 %0, %1, %2, %3" : "=v"(x) : "s"(big), "v"(old), "v"(nv));
-        } else if constexpr (FORM == 5) {
-            // No C-class instruction at all: s = clamp01(1 + nv * old * 2^100) is 1 unless the signs differ (then nv * old
-            // < 0, at least 2^-86 in magnitude for values >= 2^-43, and 1 - 2^14 clamps to 0); v = nv * s + 0 (the + 0 keeps
-            // a dropped negative nv from becoming -0.0).  Needs only "no product underflows", like the multiply form.
-            float pr, sel;
-            asm("v_mul_f32_e32 %0, %1, %2" : "=v"(pr) : "v"(nv), "v"(old));
-            asm("v_fma_f32 %0, %1, %2, 1.0 clamp" : "=v"(sel) : "v"(pr), "s"(0x1p100f));
-            asm("v_fma_f32 %0, %1, %2, 0" : "=v"(r) : "v"(nv), "v"(sel));
-            return r;
-        } else {
-            asm("v_mul_legacy_f32_e64 %0, %1, %2" : "=v"(x) : "v"(old), "s"(__builtin_inff()));
-            x = x + nv;
-        }
-        asm("v_med3_f32 %0, %1, 0, %2" : "=v"(r) : "v"(nv), "v"(x));
-        return r;
-    }
-    // nv, or +0 where drop(nv, old)  (zeroing by EXEC predication instead of v_cndmask measured slower:
-    // EXEC writes stall the VALU -- DESIGN.md 4.4)
-    // FORM: 0 = compare + select, 1 = the select through keep_unless_negative (chosen per kernel, see selfcorr_form())
-    // (the clamp forms need a guarantee about the values: self_correct_b)
-    template <int FORM>
-    LDPC_DEV static R self_correct(R nv, R old)
-    {
-        if constexpr (FORM == 1) {
-            const int t = __builtin_amdgcn_bitop3_b32(__float_as_int(old), __float_as_int(nv), (int)0x80000000, 0x78);
-            return keep_unless_negative(__int_as_float(t), nv);
-        } else {
-            return select_zero(drop(nv, old), nv);
-        }
-    }
-    // The same for codewords whose LLRs passed the range vote (BOUNDED: every |LLR| <= nocap_limit and every
-    // nonzero |LLR| >= 2^-20, see begin_codeword): "old != 0 and the signs differ" is then exactly "nv * old < 0".
-    // No value is infinite (the nocap bound), and every value of the decode is a multiple of g = 2^(e_min - 23),
-    // e_min >= -20 the exponent of the smallest nonzero |LLR| (sums and differences of multiples of g round to
-    // multiples of g), so a nonzero value is at least 2^-43 and a product of two cannot underflow; nv == 0 gives
-    // v = 0 whichever way the test goes.  An F-class v_mul_f32 in place of the VOP3 bit operation: +1 %.
-    // FORM 2 / 3: the clamp forms above (FORM 2 with big = 2^126: the launch's limit then also keeps
-    // 2^126 * 2^-43 above every magnitude of the decode, nocap_limit_for()).
-    template <bool BOUNDED, int FORM = 0>
-    LDPC_DEV static R self_correct_b(R nv, R old)
-    {
-        if constexpr (BOUNDED && FORM >= 2) {
-            return clamp_to_side<FORM>(nv, old, 0x1p126f);
-        } else if constexpr (BOUNDED) {
-            float p;
-            asm("v_mul_f32_e32 %0, %1, %2" : "=v"(p) : "v"(nv), "v"(old));
-            if constexpr (FORM == 1) return keep_unless_negative(p, nv);
-            else return select_zero(p < 0.0f, nv);
-        } else {
-            return self_correct<(FORM == 1 ? 1 : 0)>(nv, old);
-        }
-    }
-    // m >= 0 has bit 31 clear, so "m with sign s_all ^ s_own" is one three-input XOR of sign words
-    LDPC_DEV static R apply_sign(R m, int s_all, int s_own)
-    {
-        return __int_as_float(__builtin_amdgcn_bitop3_b32(__float_as_int(m), s_all, s_own, 0x96));
-    }
-};
-
-// f64 LLRs (decoder.rs:78-86): two VGPRs per value, the sign is bit 31 of the HIGH word, so the
-// sign-word machinery (bits / apply_sign) works on that word; no -0.0 either (load adds +0.0).
-// Plain expressions instead of pinned instruction trees: f64 is the least used variant and its
-// VALU ops are quarter rate whatever the tree looks like.
-template <> struct Ops<double> {
-    using R = double;
-    using E = double;
-    LDPC_DEV static R zero() { return 0.0; }
-    LDPC_DEV static R maxval() { return DBL_MAX; }
-    LDPC_DEV static R load(double x) { return __builtin_fmin(x + 0.0, __builtin_inf()); }      // -0.0 -> +0.0, NaN -> +inf: see Ops<float>::load
-    LDPC_DEV static R canon_late(R x) { return __builtin_fmin(x + 0.0, __builtin_inf()); }
-    LDPC_DEV static R keep_raw(double x) { return x; }
-    LDPC_DEV static R load_nonan(double x) { return x + 0.0; }
-    LDPC_DEV static double store(R x) { return x; }
-    LDPC_DEV static R from_lds(double x) { return x; }
-    LDPC_DEV static int bits(R x) { return __double2hiint(x); }
-    static constexpr bool SIGN_WORD_IS_BIT31_ONLY = true;
-    LDPC_DEV static int sign_word(R x) { return __double2hiint(x) & (int)0x80000000; }
-    LDPC_DEV static R add(R a, R b) { return a + b; }
-    LDPC_DEV static R sub(R a, R b) { return a - b; }
-    LDPC_DEV static R sub_nv(R a, R b) { return a - b; }
-    LDPC_DEV static R mag(R x) { return __builtin_fabs(x); }
-    template <bool AX, bool AY>
-    LDPC_DEV static R min2(R x, R y)
-    {
-        const R a = AX ? __builtin_fabs(x) : x, b = AY ? __builtin_fabs(y) : y;
-        return __builtin_fmin(a, b);              // v_min_f64: a NaN operand is ignored, as the reference's `<` does (:430-434)
-    }
-    template <bool AX> LDPC_DEV static R min2_cap(R x) { return min2<AX, false>(x, DBL_MAX); }
-    template <bool AX, bool AY> LDPC_DEV static R min3_cap(R x, R y) { return min2<false, false>(min2<AX, AY>(x, y), DBL_MAX); }
-    template <bool AX, bool AY, bool AZ>
-    LDPC_DEV static R min3(R x, R y, R z) { return min2<false, AZ>(min2<AX, AY>(x, y), z); }
-    template <int FORM>
-    LDPC_DEV static R self_correct(R nv, R old)                                  // decoder.rs:422-425
-    {
-        return (old != 0.0 && (nv < 0.0) != (old < 0.0)) ? 0.0 : nv;
-    }
-    template <bool BOUNDED, int FORM = 0> LDPC_DEV static R self_correct_b(R nv, R old) { return self_correct<0>(nv, old); }
-    LDPC_DEV static R apply_sign(R m, int s_all, int s_own)
-    {
-        return __hiloint2double(__double2hiint(m) ^ s_all ^ s_own, __double2loint(m));
-    }
-};
-
-// Integer LLR types run on the float pipeline: i8/i16 values and every intermediate of the
-// algorithm are integers of magnitude <= 2^16, which f32 represents exactly, so saturating
-// add/sub (decoder.rs:47-48, :56-57) are an f32 add/sub followed by a clamp, and all the sign-bit
-// and exclusive-minimum machinery of the f32 path applies unchanged.  saturating_abs(-2^(b-1)) =
-// 2^(b-1)-1 (decoder.rs:46, :55) falls out of capping the exclusive minimum at maxval.
-template <class I, int LO, int HI> struct IntOps : Ops<float> {     // decoder.rs:42-59
-    LDPC_DEV static R maxval() { return (float)HI; }
-    LDPC_DEV static R load(I x) { return (float)(int)x; }                       // never -0.0
-    LDPC_DEV static R canon_late(R x) { return x; }
-    LDPC_DEV static R keep_raw(I x) { return (float)(int)x; }
-    LDPC_DEV static R load_nonan(I x) { return (float)(int)x; }
-    LDPC_DEV static R clamp(R x) { return __builtin_amdgcn_fmed3f(x, (float)LO, (float)HI); }
-    LDPC_DEV static R add(R a, R b) { return clamp(a + b); }                    // saturating_add
-    LDPC_DEV static R sub(R a, R b) { return clamp(a - b); }                    // saturating_sub
-    // The new v of an edge, decoder.rs:421, WITHOUT the clamp of saturating_sub: v is only ever used through its
-    // sign, its zero-ness (both unchanged by the clamp) and min(|v|, maxval) inside the capped exclusive minimum
-    // (saturating_abs of the clamped value IS min(|a - b|, maxval), whichever end clamped), so the clamp is dead
-    // work; a - b is exact in f32 (|a - b| < 2^17).  One v_med3 less per edge and iteration.
-    LDPC_DEV static R sub_nv(R a, R b) { return a - b; }
-    LDPC_DEV static R mag(R x) { return __builtin_fminf(__builtin_fabsf(x), (float)HI); }   // saturating_abs
-    // (the sign word of an integer message as 0.0 * x = +-0.0 -- a float multiply instead of a v_and -- measures 0 to -2 %:
-    // profiles/r03_kbench/kb19_sign_by_mul.txt)
-    // Self-correction test of decoder.rs:422 for integer-valued messages: old != 0 and the signs differ exactly
-    // when the product is negative -- |nv|, |old| < 2^17, so the f32 product can neither underflow to zero nor
-    // lose its sign (it may round), and nv == 0 gives v = 0 whichever way the test goes.  An F-class v_mul_f32
-    // (co-issues with the 4-cycle instructions of other waves) instead of the VOP3 bit operation of the f32 path,
-    // where the same trick would need a vote on the LLR range (+1 %).
-    LDPC_DEV static bool drop(R nv, R old)
-    {
-        float p;
-        asm("v_mul_f32_e32 %0, %1, %2" : "=v"(p) : "v"(nv), "v"(old));
-        return p < 0.0f;
-    }
-    // FORM 2 / 3: the clamp forms of Ops<float>::clamp_to_side -- exact for every integer message: |nv| < 2^17 and a
-    // nonzero |old| >= 1, so 2^20 * |old| > |nv| always
-    // FORM 6: form 5 without its multiply.  Integer messages are zero or at least 1 in magnitude, so nv * old is <= -1 when
-    // the signs differ, >= 1 when they agree and 0 when either is zero: s = clamp01(fma(nv, old, 1)) is 0 / 1 / 1 with no scale
-    // factor, and v = fma(nv, s, 0).  Two full-rate instructions per update and no 4-cycle one (form 2: fma + med3, form 5:
-    // mul + fma + fma).  The product is below 2^33 and rounds, but never across zero.
-    template <int FORM>
-    LDPC_DEV static R self_correct(R nv, R old)
-    {
-        if constexpr (FORM == 6) {
-            float sel, r;
-            asm("v_fma_f32 %0, %1, %2, 1.0 clamp" : "=v"(sel) : "v"(nv), "v"(old));
-            asm("v_fma_f32 %0, %1, %2, 0" : "=v"(r) : "v"(nv), "v"(sel));
-            return r;
-        } else if constexpr (FORM >= 2) {
-            return Ops<float>::clamp_to_side<FORM>(nv, old, 0x1p20f);
-        } else if constexpr (FORM == 1) {
-            float p;
-            asm("v_mul_f32_e32 %0, %1, %2" : "=v"(p) : "v"(nv), "v"(old));
-            return Ops<float>::keep_unless_negative(p, nv);
-        } else {
-            return Ops<float>::select_zero(drop(nv, old), nv);
-        }
-    }
-    template <bool BOUNDED, int FORM = 0> LDPC_DEV static R self_correct_b(R nv, R old) { return self_correct<FORM>(nv, old); }
-    template <bool AX>
-    LDPC_DEV static R min2_cap(R x)
-    {
-        R d;
-        const float cap = (float)HI;
-        if constexpr (AX) asm("v_min_f32_e64 %0, |%1|, %2" : "=v"(d) : "v"(x), "s"(cap));
-        else asm("v_min_f32_e32 %0, %2, %1" : "=v"(d) : "v"(x), "s"(cap));
-        return d;
-    }
-    template <bool AX, bool AY>
-    LDPC_DEV static R min3_cap(R x, R y)
-    {
-        R d;
-        const float cap = (float)HI;
-        if constexpr (AX && AY) asm("v_min3_f32 %0, |%1|, |%2|, %3" : "=v"(d) : "v"(x), "v"(y), "s"(cap));
-        else if constexpr (!AX && !AY) asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "s"(cap));
-        else d = min2_cap<false>(Ops<float>::min2<AX, AY>(x, y));
-        return d;
-    }
-};
-template <> struct Ops<int8_t>  : IntOps<int8_t, -128, 127> {};
-template <> struct Ops<int16_t> : IntOps<int16_t, -32768, 32767> {};
-
-// i32 LLRs (decoder.rs:60-68): genuine 32-bit integer arithmetic -- the f32 pipeline is exact only to 2^24.
-// Saturating add/sub are v_add_i32 / v_sub_i32 with the clamp bit.  Those, every integer min / max / compare and the three-operand
-// integer forms issue at HALF the rate of v_xor / v_sub_u32 / v_ashrrev / v_bitop3 on gfx950 (tools/ubench/wide_rate.hip: 1.8 against
-// 0.95 ns per wave-instruction and SIMD), which is why decode_ms::<i32> runs at about half decode_ms::<f32>'s rate (f32 add / sub / fma
-// are full rate, |x| is a free source modifier there and the sign application one v_bitop3).  Round 6 moved what it could to
-// full-rate operations (TM8192 i32 4.24 -> see profiles/r06_final/rates_all_codes.txt):
-//   * the self-correction without a compare (self_correct below: four full-rate operations for xor + two v_cmp + s_and + select);
-//   * the MAGNITUDE as the wrapping |x| (one v_sub_u32 + one v_max_i32 instead of v_sub_i32 clamp + v_max_i32).  It wraps where
-//     saturating_abs saturates -- |INT_MIN| comes out as 0x80000000 instead of INT_MAX (:64) -- so magnitudes are compared UNSIGNED and
-//     every exclusive minimum is capped at maxval = INT_MAX (which decoder.rs:414-415 does anyway: min1 / min2 start there):
-//     min(sat|a|, ...) = min_u32(wrap|a|, INT_MAX, ...).  The cap rides in a v_min3_u32's third operand except on rows of degree 2 and
-//     4-6 (one operation more per three edges).
-//   (Sign words as x >> 31 -- which would also save the shift in apply_sign -- were measured at the compiler: 118 spilled registers
-//   in the TM8192 pair kernel against 1; not adopted.)
-// "Negative" is bit 31, so the sign-word machinery applies unchanged.  The LDS element is a 4-byte container (float) holding the
-// integer's bits, which lets the pair kernel's 64-bit accesses carry it.
-template <> struct Ops<int32_t> {
-    using R = int;
-    using E = float;
-    LDPC_DEV static R zero() { return 0; }
-    LDPC_DEV static R maxval() { return 0x7FFFFFFF; }                           // :63
-    LDPC_DEV static R load(int32_t x) { return x; }
-    LDPC_DEV static R canon_late(R x) { return x; }
-    LDPC_DEV static R keep_raw(int32_t x) { return x; }
-    LDPC_DEV static R load_nonan(int32_t x) { return x; }
-    LDPC_DEV static float store(R x) { return __int_as_float(x); }
-    LDPC_DEV static R from_lds(float x) { return __float_as_int(x); }
-    LDPC_DEV static int bits(R x) { return x; }
-    static constexpr bool SIGN_WORD_IS_BIT31_ONLY = true;
-    LDPC_DEV static int sign_word(R x) { return x & (int)0x80000000; }
-    LDPC_DEV static R add(R a, R b) { R d; asm("v_add_i32 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b)); return d; }   // :65
-    LDPC_DEV static R sub(R a, R b) { R d; asm("v_sub_i32 %0, %1, %2 clamp" : "=v"(d) : "v"(a), "v"(b)); return d; }   // :66
-    LDPC_DEV static R sub_nv(R a, R b) { return sub(a, b); }                    // (32-bit: the clamp is what keeps it from wrapping)
-    // |x| as an UNSIGNED word (wraps INT_MIN to 0x80000000 where :64 saturates to INT_MAX): see above
-    LDPC_DEV static R mag(R x) { const R s = x >> 31; return (R)((unsigned)(x ^ s) - (unsigned)s); }
-    LDPC_DEV static R umin(R a, R b) { return (unsigned)b < (unsigned)a ? b : a; }
-    template <bool AX, bool AY>
-    LDPC_DEV static R min2(R x, R y)
-    {
-        const R a = AX ? mag(x) : x, b = AY ? mag(y) : y;
-        return umin(a, b);
-    }
-    template <bool AX> LDPC_DEV static R min2_cap(R x) { return umin(AX ? mag(x) : x, maxval()); }
-    template <bool AX, bool AY> LDPC_DEV static R min3_cap(R x, R y) { return umin(min2<AX, AY>(x, y), maxval()); }
-    template <bool AX, bool AY, bool AZ>
-    LDPC_DEV static R min3(R x, R y, R z) { return min2<false, AZ>(min2<AX, AY>(x, y), z); }
-    // decoder.rs:422-425: v = 0 where the old v is non-zero and of the other sign, else nv -- without a compare: bit 31 of
-    // (nv ^ old) & (old | -old) says "drop" (old | -old has bit 31 set exactly for old != 0, INT_MIN included); an arithmetic shift
-    // spreads it over the word and it is cleared out of nv: v_sub_u32, v_bitop3, v_ashrrev, v_bitop3 -- all full rate
-    template <int FORM>
-    LDPC_DEV static R self_correct(R nv, R old)
-    {
-        const int negold = (int)(0u - (unsigned)old);
-        const int drop = __builtin_amdgcn_bitop3_b32(nv, old, negold, 0x2C) >> 31;          // (a ^ b) & (b | c)
-        return __builtin_amdgcn_bitop3_b32(nv, drop, drop, 0x30);                           // a & ~b
-    }
-    template <bool BOUNDED, int FORM = 0> LDPC_DEV static R self_correct_b(R nv, R old) { return self_correct<0>(nv, old); }
-    // m >= 0 negated when the product of the other edges' signs is negative (:398-405)
-    LDPC_DEV static R apply_sign(R m, int s_all, int s_own)
-    {
-        const int k = (s_all ^ s_own) >> 31;                                     // 0 or -1
-        return (m ^ k) - k;
-    }
-};
-
-// e[i] = min(maxval, min over j != i of a[j]).  Equals what decoder.rs:391-395 selects from
-// (min1, min2): min2 if |v_i| is a smallest magnitude of the check, min1 otherwise -- and
-// min1/min2 start at maxval (decoder.rs:414-415) and are only replaced by strictly smaller
-// values (:430-434), hence the clamp.  Elements are grouped in threes so that one min3 per
-// element finishes the job: ~1.7 operations per edge at degree 6, ~1.9 at degree 18.
-template <class O, int D, bool ABS, bool CAP = true>
-LDPC_DEV void exclusive_min(const typename O::R (&a)[D], typename O::R (&e)[D])
-{
-    // CAP = false: the caller guarantees that every magnitude is below maxval (then the clamp is the
-    // identity); only checks of degree >= 4 save operations by it
-    using R = typename O::R;
-    const R MX = O::maxval();
-    if constexpr (D == 1) {
-        e[0] = MX;
-    } else if constexpr (D == 2) {
-        if constexpr (CAP) {
-            e[0] = O::template min2_cap<ABS>(a[1]);
-            e[1] = O::template min2_cap<ABS>(a[0]);
-        } else {
-            e[0] = ABS ? O::mag(a[1]) : a[1];
-            e[1] = ABS ? O::mag(a[0]) : a[0];
-        }
-    } else if constexpr (D == 3) {
-        e[0] = O::template min3_cap<ABS, ABS>(a[1], a[2]);
-        e[1] = O::template min3_cap<ABS, ABS>(a[0], a[2]);
-        e[2] = O::template min3_cap<ABS, ABS>(a[0], a[1]);
-    } else {
-        constexpr int G = (D + 2) / 3;
-        R t[G], x[G];
-        static_for<0, G>([&](auto g_) LDPC_INLINE {
-            constexpr int g = decltype(g_)::value, n = (3 * g + 3 <= D) ? 3 : D - 3 * g;
-            if constexpr (n == 3) t[g] = O::template min3<ABS, ABS, ABS>(a[3 * g], a[3 * g + 1], a[3 * g + 2]);
-            else if constexpr (n == 2) t[g] = O::template min2<ABS, ABS>(a[3 * g], a[3 * g + 1]);
-            else t[g] = ABS ? O::mag(a[3 * g]) : a[3 * g];
-        });
-        exclusive_min<O, G, false, CAP>(t, x);
-        static_for<0, G>([&](auto g_) LDPC_INLINE {
-            constexpr int g = decltype(g_)::value, n = (3 * g + 3 <= D) ? 3 : D - 3 * g;
-            if constexpr (n == 3) {
-                e[3 * g]     = O::template min3<ABS, ABS, false>(a[3 * g + 1], a[3 * g + 2], x[g]);
-                e[3 * g + 1] = O::template min3<ABS, ABS, false>(a[3 * g],     a[3 * g + 2], x[g]);
-                e[3 * g + 2] = O::template min3<ABS, ABS, false>(a[3 * g],     a[3 * g + 1], x[g]);
-            } else if constexpr (n == 2) {
-                e[3 * g]     = O::template min2<ABS, false>(a[3 * g + 1], x[g]);
-                e[3 * g + 1] = O::template min2<ABS, false>(a[3 * g],     x[g]);
-            } else {
-                e[3 * g] = x[g];
-            }
-        });
-    }
-}
 
 // ---- LDS layout of one codeword: [ first half of the xu slots | xva columns | rest of xu | flags ]
 constexpr int lds_xu_off(const Prototype &p, int slot, int blk_bytes)
@@ -601,14 +71,6 @@ constexpr int lds_bias(const Prototype &p, int b, int blk_bytes)
     return a0 < a1 ? a0 : a1;
 }
 
-// rank of local edge (S, B) among a thread's local edges, index-major
-constexpr int local_edge_rank(const Prototype &p, int S, int B)
-{
-    int nloc = 0, r = 0;
-    for (int b = 0; b < p.n_blocks; ++b)
-        if (blk_local(p.blk[b])) { if (b < B) ++r; ++nloc; }
-    return S * nloc + r;
-}
 // local-edge updates done in the variable phase (see LOCAL_IN_VAR in the kernel body)
 template <int CODE, class T, int IPT, int LEAN>
 constexpr int local_in_var_default()
@@ -636,11 +98,12 @@ template <int CODE, int IPT>
 constexpr int Geometry_G() { return CODES[CODE].m / IPT >= 64 ? 1 : 64 / (CODES[CODE].m / IPT); }      // codewords per workgroup (Geometry::G)
 
 // Form of the self-correction in decode_ms_kernel (Ops<float>::clamp_to_side): 0 = compare / borrow + select, 2 = v_fma +
-// v_med3, 3 = v_mul_legacy + v_add + v_med3, 5 = three full-rate operations and no median, 6 = two (integer messages only:
+// v_med3, 3 = v_mul_legacy + v_add + v_med3, 6 = two full-rate operations and no median (integer messages only:
 // IntOps::self_correct).  This is the DEFAULT of the
 // kernel's FORM template parameter; for the f32 kernels with a clamp-free loop the launcher instantiates 2 and 3 and picks by
 // max_iters (form 2 narrows the range vote: nocap_limit_for()).
-// Same-process A/B (tools/kbench.hip, profiles/r03_kbench/kb11_forms.txt; identical outputs), M codewords/s, forms 0 / 2 / 3 / 5:
+// Same-process A/B (tools/kbench.hip, profiles/r03_kbench/kb11_forms.txt; identical outputs), M codewords/s, forms 0 / 2 / 3 / 5
+// (5 = the retired float form of 6, with a multiply and a 2^100 scale: docs/experiments.md):
 //   TM6144 i8 11.63 / 12.26 / - / 12.13;  TM2048 i8 46.9 / 49.37 / 47.74 / 48.26;  TC512 i8 (3 dB) 312.5 / 318.4 / - / -;
 //   the register-lean kernels (form 0 = the borrow form there): TM5120 i8 4 dB 20.76 / 20.74 / - / 21.08, 2 dB 7.87 / 7.85 / - /
 //   7.98; TM1280 i8 77.96 / - / - / 81.44 -- their chunked check rows like the all-full-rate form best;
@@ -667,16 +130,6 @@ constexpr bool has_nocap_loop()
     constexpr bool code = CODE == TM2048 || CODE == TC512 || CODE == TM1536;
     return LDPC_NOCAP != 0 && std::is_same_v<T, float> && code && Geometry_G<CODE, IPT>() == 1 && LEAN == 0 && IPT == 1;
 }
-
-// The in-phase verdict of the register-lean kernels (LEAN_VERDICT in the kernel body).  Measured and refuted in round 3
-// (profiles/r03_kbench/kb3.txt): carrying the rows' state across the vote costs 67 spilled registers at the lean kernels'
-// 128-register budget -- TM5120 i8 19.04 -> 17.66 (4 dB), 7.33 -> 6.71 (2 dB), f32 13.7 -> 9.6 M codewords/s.  Off.
-template <int CODE, class T>
-constexpr bool lean_verdict_default() { return false; }
-
-// Packed LLR registers in the register-lean kernels of the narrow types (PACKED_LLR in the kernel body)
-template <int CODE, class T>
-constexpr bool packed_llr_default() { return true; }
 
 // Kernels that run iteration 0 as a pass of its own (PEEL_FIRST in the kernel body).  Same-process A/B, M codewords/s:
 //   TC128 f32 1863 -> 2067, i8 1806 -> 2061; TC256 894 -> 1025 / 946 -> 1095; TC512 539 -> 598 / 555 -> 676 (5 dB);
@@ -729,31 +182,6 @@ struct Geometry {
     static_assert(M % IPT == 0 && NT >= 8 && (NT & (NT - 1)) == 0, "bad IPT");
 };
 
-// pi_k(i) for check index i whose quarter j = i / (M/4) the caller supplies: a literal when a
-// thread's indices never leave a quarter, a wave-uniform scalar when waves do not straddle
-// quarters (then the selects below are scalar), a per-lane value otherwise.
-template <int K, int M>
-LDPC_DEV int pi_dev(int i, int j)
-{
-    constexpr int LQ = ilog2(M / 4), Q = M / 4;
-    constexpr int P0 = phi_of(K, 0, M), P1 = phi_of(K, 1, M), P2 = phi_of(K, 2, M), P3 = phi_of(K, 3, M);
-    constexpr int TH = theta_of(K);
-    int phi;
-    if constexpr (Q <= 256) {
-        // the four rotations of a block (each < Q <= 256) packed into one literal and picked by a bit-field
-        // extract: one VALU operation.  Written as a chain of selects on the per-lane quarter the compiler
-        // emitted EXEC-masked branches, one pair per quarter and edge (119 of them in the TM1280 kernel).
-        constexpr unsigned PACK = (unsigned)P0 | ((unsigned)P1 << 8) | ((unsigned)P2 << 16) | ((unsigned)P3 << 24);
-        phi = (int)__builtin_amdgcn_ubfe(PACK, (unsigned)j * 8u, 8u);
-    } else {
-        // rotations up to 16 bits: two literals, one select on bit 1 of the quarter, one bit-field extract
-        constexpr unsigned LO = (unsigned)P0 | ((unsigned)P1 << 16), HI = (unsigned)P2 | ((unsigned)P3 << 16);
-        const unsigned w = (j & 2) ? HI : LO;
-        phi = (int)__builtin_amdgcn_ubfe(w, ((unsigned)j & 1u) * 16u, 16u);
-    }
-    return (((TH + j) & 3) << LQ) + ((phi + i) & (Q - 1));
-}
-
 // JW >= 0: the body is specialised for waves whose indices start in quarter JW (the kernel
 // branches once, wave-uniformly, into the matching copy) so that every rotation constant of the
 // pi_k blocks is a literal; JW < 0: generic body, constants in SGPRs.
@@ -771,22 +199,13 @@ LDPC_DEV int pi_dev(int i, int j)
 template <int CODE, class T, int IPT, int LEAN>
 constexpr bool llr_in_lds() { return (CODE == TC512 || CODE == TC128) && std::is_same_v<T, float> && IPT == 1 && LEAN == 0; }
 
-// A marginal as an element of the LLR type: the integer types' registers hold exact integers inside the type's range (IntOps),
-// the others are the type itself.
-template <class T, class R>
-LDPC_DEV T soft_value(R x)
-{
-    if constexpr (std::is_same_v<T, int8_t> || std::is_same_v<T, int16_t>) return (T)(int)x;
-    else return (T)x;
-}
-
 // SOFT: the form with soft output -- every codeword's marginals (decoder.rs:377, the `va` decode_ms returns with) are also stored
 // to `app` ([batch][n + p], the LLR type), one unit-stride store per owned variable in the epilogue (DESIGN.md "Soft output").
 // The hard-only kernels are SOFT = false, where all of it compiles away.
-template <int CODE, class T, int IPT, bool PF, int LEAN, int JW, int FORM, int NANPASS = 0, bool SOFT = false>
+template <int CODE, class T, int IPT, int LEAN, int JW, int FORM, int NANPASS = 0, bool SOFT = false>
 LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                              uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
-                             uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k, char *lds, char *stage,
+                             uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k, char *lds,
                              T *__restrict__ app = nullptr)
 {
     using GEO = Geometry<CODE, T, IPT>;
@@ -822,11 +241,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     constexpr bool LLR_LDS = llr_in_lds<CODE, T, IPT, LEAN>();
     constexpr int LLR_OFF = FLAG_OFF + 16;
     constexpr int GROUP_BYTES = (FLAG_OFF + 8 + 15) / 16 * 16 + (LLR_LDS ? NTX * M * SZ : 0);
-    static_assert(!LLR_LDS || (!INPLACE && !PF && FLAG_OFF % 16 == 0));
-    static_assert(!PF || (G == 1 && NT >= 64), "LLR staging needs whole waves per codeword");
-    constexpr int TSZ = sizeof(T);
-    constexpr int STAGE_BYTES = PF ? N * TSZ : 0;
-    (void)STAGE_BYTES;
+    static_assert(!LLR_LDS || (!INPLACE && FLAG_OFF % 16 == 0));
 
     const int tid = threadIdx.x;
     const int grp = G == 1 ? 0 : tid / NT;
@@ -915,40 +330,19 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     using FW = std::conditional_t<(IPT * NB <= 32), unsigned, unsigned long long>;
     FW vneg = 0, vnz = 0;         // bit S*NB+B: v of that edge is negative / non-zero
 
-    // Asynchronous global -> LDS copy of codeword `c`'s LLRs into the staging buffer.  Each wave
-    // stages exactly the elements its own lanes will read back, so only the issuing wave's
-    // vmcnt has to be waited for, never a barrier.  `stage` is a separate __shared__ object so
-    // that the compiler does not order the decode loop's LDS traffic behind these copies.
-    auto stage_issue = [&](uint32_t c) LDPC_INLINE {
-        if constexpr (PF) {
-            unsigned tu = (unsigned)t;
-            asm volatile("" : "+v"(tu));
-            static_for<0, IPT>([&](auto S_) LDPC_INLINE {
-                static_for<0, NTX>([&](auto C_) LDPC_INLINE {
-                    constexpr int S = decltype(S_)::value, C = decltype(C_)::value;
-                    const T *src = (llrs + (size_t)c * N) + ((unsigned)(C * M + S * NT) + tu);   // scalar base + lane offset
-                    char *dst = stage + (C * M + S * NT + (t & ~63)) * TSZ;           // wave-uniform
-                    auto gsrc = (const __attribute__((address_space(1))) void *)src;
-                    auto ldst = (__attribute__((address_space(3))) void *)dst;
-                    // the size operand must be a literal
-                    if constexpr (TSZ == 4) __builtin_amdgcn_global_load_lds(gsrc, ldst, 4, 0, 0);
-                    else if constexpr (TSZ == 2) __builtin_amdgcn_global_load_lds(gsrc, ldst, 2, 0, 0);
-                    else __builtin_amdgcn_global_load_lds(gsrc, ldst, 1, 0, 0);
-                });
-            });
-        }
-    };
-
     // Plain global loads of codeword `c`'s LLRs into registers.  Issued BEFORE the previous
     // codeword's hard-decision epilogue and this one's state initialisation, whose ~200
     // instructions cover the HBM latency; the registers are the ones `llr` vacates when a decode ends.
+    // (Staging the NEXT codeword's LLRs in LDS with asynchronous global -> LDS copies during the current decode measured
+    // SLOWER than these loads on TM8192 -- 4.99 against 5.29 M codewords/s: the extra live state costs spills at the
+    // 128-VGPR budget -- and is retired: DESIGN.md section 7, docs/experiments.md.)
     T lraw[IPT][NTX];
     bool cap_wave = false;        // one-wave workgroups: the clamp vote of the current codeword (wave-uniform)
     // The register-lean kernels of the narrow LLR types keep their LLRs as PACKED raw values -- four i8 or two i16 per register,
     // three / five registers for TM5120's ten -- instead of re-reading them from L2 in every variable phase, as the lean f32
     // kernel must (it has no registers to spare): TM5120 i8 19.04 -> 20.64 (4 dB), 7.33 -> 7.84 M codewords/s (2 dB), no spills
     // (profiles/r03_kbench/kb3.txt).  Unpacking is a shift-and-sign-extend folded into the conversion to f32.
-    constexpr bool PACKED_LLR = LEAN == 1 && sizeof(T) <= 2 && packed_llr_default<CODE, T>();
+    constexpr bool PACKED_LLR = LEAN == 1 && sizeof(T) <= 2;
     constexpr int PER_REG = PACKED_LLR ? 4 / (int)sizeof(T) : 1, PK_BITS = 8 * (int)sizeof(T);
     unsigned llr_pk[IPT][(NTX + PER_REG - 1) / PER_REG];
     auto fetch_llrs = [&](uint32_t c) LDPC_INLINE {
@@ -984,19 +378,15 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     // which re-read their LLRs in every variable phase, and TM1280 f32
     constexpr bool NONAN = NANPASS == 1;         // first of two passes: NaN LLRs are only looked for (the codeword is marked), not handled
     constexpr bool REDO = NANPASS == 2;          // second pass: only the codewords the first one marked
-    static_assert(NANPASS == 0 || (std::is_floating_point_v<T> && LEAN == 1 && G == 1 && !PF && GEO::WG > 64), "two-pass NaN handling: the register-lean float kernel, one multi-wave codeword per workgroup");
+    static_assert(NANPASS == 0 || (std::is_floating_point_v<T> && LEAN == 1 && G == 1 && GEO::WG > 64), "two-pass NaN handling: the register-lean float kernel, one multi-wave codeword per workgroup");
     constexpr bool LATE_CANON = std::is_floating_point_v<T> && (LEAN != 0 || (CODE == TM1280 && IPT == 1)) && !NONAN;
     // (Tried for the register-lean f32 kernel, which cannot afford even that -- 45 more spilled registers, TM5120 f32 17.1 ->
     // 14.4 M codewords/s: look for a NaN among a codeword's LLRs once, before the first pass, and run a second copy of the loop
     // that canonicalises only for codewords that have one.  The second copy alone costs more: 120 spilled registers, 13.3 M
-    // codewords/s (LDPC_NANVOTE, kbench only; profiles/r03_kbench/kb16_nanvote.txt).  The vote survives as the MARK of the
+    // codewords/s (profiles/r03_kbench/kb16_nanvote.txt; retired: docs/experiments.md).  The vote survives as the MARK of the
     // two-pass form: the common copy is the whole first kernel, the canonicalising copy a second kernel.)
-    constexpr bool NANVOTE = false;
     constexpr bool ZERO_FREE = PEEL_FIRST;
-    auto begin_codeword = [&](bool staged) LDPC_INLINE {
-        if constexpr (PF) {
-            if (staged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+    auto begin_codeword = [&]() LDPC_INLINE {
         int tb = t * SZ;
         unsigned tu = (unsigned)t;
         asm volatile("" : "+v"(tb), "+v"(tu));   // keep the address arithmetic inside the loop (see check_phase)
@@ -1024,8 +414,12 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
             }
             static_for<0, NTX>([&](auto C_) LDPC_INLINE {
                 constexpr int C = decltype(C_)::value;
-                if (PF && staged) llr[S][C] = O::load(*reinterpret_cast<const T *>(stage + (C * M + i) * TSZ));
-                else if constexpr (!LEAN) llr[S][C] = LATE_CANON ? O::keep_raw(lraw[S][C]) : O::load(lraw[S][C]);     // fetched by fetch_llrs()
+                // (Names `lds` only so that this closure captures it, as it captured the staging buffer until LLR staging was retired:
+                // without the capture the compiler promotes the f64 TC128 / TC256 kernels' two queue words in the other order and
+                // numbers two constant SGPR pairs the other way round -- the same instructions, but not the measured binary.
+                // Drop it with the next change that re-measures those kernels.)
+                (void)lds;
+                if constexpr (!LEAN) llr[S][C] = LATE_CANON ? O::keep_raw(lraw[S][C]) : O::load(lraw[S][C]);     // fetched by fetch_llrs()
                 if constexpr (LLR_LDS) lds_store(LLR_OFF + (C * M + i) * SZ, O::store(llr[S][C]));      // (llr[][] dies after the range vote below)
             });
         });
@@ -1041,15 +435,6 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
             });
             if constexpr (GEO::WG == 64) cap_wave = __ballot(big) != 0;          // one wave = one codeword: no LDS word needed
             else if (__ballot(big) != 0 && (tid & 63) == 0) cap_flag() = 1;
-        } else if constexpr (NANVOTE) {
-            bool nn = false;
-            static_for<0, IPT>([&](auto S_) LDPC_INLINE {
-                static_for<0, NTX>([&](auto C_) LDPC_INLINE {
-                    const T x = (llrs + (size_t)(live ? cw : 0) * N)[(unsigned)(decltype(C_)::value * M + decltype(S_)::value * NT) + (unsigned)t];
-                    nn |= x != x;
-                });
-            });
-            if (__ballot(nn) != 0 && (tid & 63) == 0) cap_flag() = 1;           // (the clamp-vote word serves as the NaN vote here)
         } else {
             if (t == 2) *reinterpret_cast<int *>(gbase + FLAG_OFF + 8) = 0;  // (the clamp-vote word, unused here)
         }
@@ -1097,10 +482,8 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     // One iteration of message passing for this thread's indices: the two phases below.
     // FIRST_: iteration 0 of a codeword, peeled by kernels with PEEL_FIRST -- every u is zero, so the marginals are the
     // LLRs and nothing is read from LDS
-    // CANON_ (NANVOTE kernels): this codeword has a NaN LLR -- canonicalise the finished marginals; 0 = the common copy
-    auto variable_phase = [&](auto FIRST_, auto CANON_) LDPC_INLINE {
+    auto variable_phase = [&](auto FIRST_) LDPC_INLINE {
         constexpr bool FIRST = decltype(FIRST_)::value != 0;
-        constexpr bool CANON = LATE_CANON && (!NANVOTE || decltype(CANON_)::value != 0);
         // marginals (decoder.rs:382-383, :408)
         int tv = t;
         if constexpr (INPLACE) asm volatile("" : "+v"(tv));     // keep the (large-offset) LDS addresses out of loop-carried VGPRs
@@ -1118,8 +501,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
                         const T x = (llrs + (size_t)(live ? cw : 0) * N)[(unsigned)(C * M) + (unsigned)i];
                         // (first of two NaN passes: the raw value here and `+ 0.0` on the finished marginal, as canon_late does it --
                         // with the `+ 0.0` up here the lean TM5120 kernel spills 53 registers instead of 8)
-                        acc = (CANON || NONAN) ? O::keep_raw(x) : (NANVOTE ? O::load_nonan(x) : O::load(x));
-                        
+                        acc = (LATE_CANON || NONAN) ? O::keep_raw(x) : O::load(x);
                     }
                     else if constexpr (LLR_LDS) acc = O::from_lds(lds_load(LLR_OFF + (C * M + i) * SZ));
                     else acc = llr[S][C];
@@ -1135,7 +517,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
                             acc = O::add(acc, ue[B]);                                  // :408
                         }
                     });
-                    if constexpr (CANON && C < NTX) acc = O::canon_late(acc);        // (see Ops<float>::canon_late)
+                    if constexpr (LATE_CANON && C < NTX) acc = O::canon_late(acc);        // (see Ops<float>::canon_late)
                     else if constexpr (NONAN && C < NTX) acc = O::load_nonan(acc);
                     if constexpr (col_slot(P, C) < 0) va[S][C] = acc;               // exchanged columns: only the sign word is kept (hi array)
                     static_for<0, NB>([&](auto B_) LDPC_INLINE {                       // nv = va - u (:421), in place
@@ -1162,7 +544,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
                         else acc = O::add(acc, u[S][B]);
                     }
                 });
-                if constexpr (CANON && C < NTX) acc = O::canon_late(acc);          // (see Ops<float>::canon_late)
+                if constexpr (LATE_CANON && C < NTX) acc = O::canon_late(acc);          // (see Ops<float>::canon_late)
                 else if constexpr (NONAN && C < NTX) acc = O::load_nonan(acc);
                 va[S][C] = acc;
                 constexpr int cs = col_slot(P, C);
@@ -1195,12 +577,11 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     constexpr int WG_VERDICT_SET = LDPC_WG_VERDICT >= 0 ? LDPC_WG_VERDICT
                                  : (CODE == TM1536 || (CODE == TM1280 && !(sizeof(T) <= 2))) ? 1 : 0;
     constexpr bool WG_VERDICT = WG_VERDICT_SET != 0 && !WAVE_VERDICT && G == 1 && IPT == 1 && LEAN == 0;
-    // The register-lean check phase cannot hold its marginals between a parity pass and the updates (that is what makes it
-    // lean), but it can split the other way: pass A = requests, edge updates, parities and sign words of ALL rows; vote
-    // through the flag and a third barrier; pass B = exclusive minima, next u and their stores, skipped on success (it reads
-    // only v, which is in registers).  LDPC_LEAN_VERDICT: measured in round 3 (see lean_verdict_default()).
-    constexpr bool LEAN_VERDICT = (LDPC_LEAN_VERDICT >= 0 ? LDPC_LEAN_VERDICT != 0 : lean_verdict_default<CODE, T>()) && LEAN == 1 && G == 1;
-    constexpr bool IN_PHASE_VERDICT = WAVE_VERDICT || WG_VERDICT || LEAN_VERDICT;
+    constexpr bool IN_PHASE_VERDICT = WAVE_VERDICT || WG_VERDICT;
+    // (The register-lean check phase has no in-phase verdict.  It cannot hold its marginals between a parity pass and the updates --
+    // that is what makes it lean -- and splitting it the other way, all rows' updates and parities, a vote through the flag and a
+    // third barrier, then the minima and next u, carried the rows' state across the vote: 67 spilled registers at the lean kernels'
+    // 128-register budget, TM5120 i8 19.04 -> 17.66 M codewords/s.  Retired: docs/experiments.md.)
     // Iteration 0 peeled (PEEL_FIRST; at high SNR a decode is two or three passes, and the first one is cheaper than
     // the rest): u = 0 and v = 0 make every new v the marginal itself (decoder.rs:421-425
     // with u == 0 and v == 0: x - 0, kept), so the pass needs no LDS reads in its variable phase and no
@@ -1348,8 +729,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
         int par_any = 0;
         int tb = t * SZ;
         asm volatile("" : "+v"(tb));
-        int sgn_row[IPT][NROWS];                                  // (LEAN_VERDICT: the rows' sign words, carried from pass A to pass B)
-        // pass B of one row: exclusive minima, next u, stores (decoder.rs:391-405 of the next iteration)
+        // the second half of one row: exclusive minima, next u, stores (decoder.rs:391-405 of the next iteration)
         auto finish_row = [&](auto S_, auto R_, int sgn) LDPC_INLINE {
             constexpr int S = decltype(S_)::value, Rw = decltype(R_)::value;
             constexpr int D = row_degree(P, Rw);
@@ -1423,25 +803,12 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
                 });
                 static_assert(O::SIGN_WORD_IS_BIT31_ONLY, "the register-lean check phase forms sign words from raw bits");
                 const int sgn = sgnw & (int)0x80000000;
-                if constexpr (LEAN_VERDICT) sgn_row[S][Rw] = sgn;
-                else finish_row(S_, R_, sgn);
+                finish_row(S_, R_, sgn);
                 par_any |= par;
             });
         });
-        if constexpr (LEAN_VERDICT) {
-            if (__ballot(par_any < 0) != 0 && (tid & 63) == 0) flag_at(it) = 1;
-            LDPC_SYNC();
-            if (flag_at(it) == 0) return true;                                         // :453: every check of the codeword holds
-            tb = t * SZ;
-            asm volatile("" : "+v"(tb));          // pass B recomputes its addresses: none may stay live across the vote
-            static_for<0, IPT>([&](auto S_) LDPC_INLINE {
-                static_for<0, NROWS>([&](auto R_) LDPC_INLINE { finish_row(S_, R_, sgn_row[decltype(S_)::value][decltype(R_)::value]); });
-            });
-            return false;
-        } else {
-            if (par_any < 0) flag_at(it) = 1;
-            return false;
-        }
+        if (par_any < 0) flag_at(it) = 1;
+        return false;
     };
 
     // In-place check phase (LEAN == 2): as the lean one, but an exchanged edge's slot already holds
@@ -1543,7 +910,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
         }
     };
 
-    if constexpr ((NOCAP_POSSIBLE && GEO::WG != 64) || NANVOTE || NONAN) { if (t == 0) cap_flag() = 0; LDPC_SYNC(); }
+    if constexpr ((NOCAP_POSSIBLE && GEO::WG != 64) || NONAN) { if (t == 0) cap_flag() = 0; LDPC_SYNC(); }
     // Second NaN pass: workgroup b looks through the groups b, b + gridDim.x, ... for the ones the first pass marked, 64 at a
     // time (one load per lane, one ballot; every wave of the workgroup computes the same wave-uniform answer).  A launch
     // without a NaN is a few such loads per workgroup.
@@ -1572,13 +939,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
         if (dyn && fresh && tid == 0) ticket = __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (!first) fetch_llrs(cw);    // (issuing them before the previous epilogue measured 1.5 % slower here: register allocation)
-    begin_codeword(!first);
-    if constexpr (PF) {
-        // the staged LLRs are in registers (the loads above were waited for by their use in
-        // O::load's consumers only after lgkmcnt; make that explicit), now refill the stage
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!dyn && CLAIM_K == 1 && g + gridDim.x < n_groups) stage_issue((uint32_t)__builtin_amdgcn_readfirstlane((int)(g + gridDim.x)));
-    }
+    begin_codeword();
 
     // Codewords that share a wave (G > 1) finish at different iterations: a finished one
     // simply stops updating (its lanes are masked off) until the whole wave is done.
@@ -1591,7 +952,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
         if (maxiters == 0) done = true;
         if constexpr (G == 1) { if (done) return; }
         else { if (__all(done)) return; }
-        if (G == 1 || !done) variable_phase(IC<1>{}, CAP_);
+        if (G == 1 || !done) variable_phase(IC<1>{});
         LDPC_SYNC();
         if (G == 1 || !done) {
             if constexpr (LEAN == 1) { if (check_phase_lean(0u, IC<1>{})) { done = true; ok = true; iters = 0; } }
@@ -1613,7 +974,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
         if constexpr (G == 1) { if (done) break; }
         else { if (__all(done)) break; }
 
-        if (G == 1 || !done) variable_phase(IC<0>{}, CAP_);
+        if (G == 1 || !done) variable_phase(IC<0>{});
         LDPC_SYNC();
         if constexpr (!WAVE_VERDICT) { if (it > 0 && t == 0) flag_at(it - 1) = 0; }
         if (G == 1 || !done) {
@@ -1625,7 +986,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     }
     };
     LDPC_SYNC();                  // the zeroed exchange slots, the flags and the clamp vote are visible
-    if constexpr (NOCAP_POSSIBLE || NANVOTE) {
+    if constexpr (NOCAP_POSSIBLE) {
         if (GEO::WG == 64 ? cap_wave : __builtin_amdgcn_readfirstlane(cap_flag()) != 0) iterate(IC<1>{});
         else iterate(IC<0>{});
     } else {
@@ -1707,12 +1068,12 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
         }
     }
     if constexpr (NONAN) {
-        static_assert(!NOCAP_POSSIBLE && !NANVOTE && NT >= 64, "first NaN pass: the clamp-vote word is the mark");
+        static_assert(!NOCAP_POSSIBLE && NT >= 64, "first NaN pass: the clamp-vote word is the mark");
         if (maxiters != 0 && __ballot(nan_seen) != 0 && (tid & 63) == 0) cap_flag() = 1;       // (zero iterations: no marginal was ever computed, and none depends on an LLR)
     } else {
         if (t == 0 && live) { iters_out[cw] = iters; success_out[cw] = ok ? 1 : 0; }
     }
-    if constexpr ((NOCAP_POSSIBLE && GEO::WG != 64) || NANVOTE) { if (t == 0) cap_flag() = 0; }
+    if constexpr (NOCAP_POSSIBLE && GEO::WG != 64) { if (t == 0) cap_flag() = 0; }
     if constexpr (!CLAIM_AHEAD) {
         if (dyn && fresh && tid == 0) ticket = __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         collect_claim();
@@ -1737,8 +1098,6 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
 }
 
 
-// PF: stage the NEXT codeword's LLRs in LDS with asynchronous global->LDS loads while the current
-// one is being decoded (costs n*sizeof(T) bytes of LDS).
 // LEAN: register-lean variant for the high-degree rate-4/5 codes (39 edges per index): the u of
 // the exchanged edges is re-read from LDS in the check phase instead of being kept in VGPRs and
 // the LLRs are re-read from global memory (L2) every iteration; this brings TM5120 under 128
@@ -1773,7 +1132,7 @@ constexpr int min_waves_per_simd()
     return 1;
 }
 
-template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM, int NANPASS, bool SOFT = false>
+template <int CODE, class T, int IPT, int LEAN, int FORM, int NANPASS, bool SOFT = false>
 __device__ __forceinline__ void decode_ms_kernel_main(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                                                       uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                                                       uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k,
@@ -1785,34 +1144,33 @@ __device__ __forceinline__ void decode_ms_kernel_main(const T *__restrict__ llrs
     constexpr int GROUP_BYTES = ((LEAN == 2 ? GEO::NX * GEO::M * ESZ + GEO::NXC * GEO::M * 4 : (GEO::NX + GEO::NXC) * GEO::M * ESZ) + 8 + 15) / 16 * 16
                                 + (llr_in_lds<CODE, T, IPT, LEAN>() ? (CODES[CODE].n / GEO::M) * GEO::M * ESZ : 0);
     __shared__ __attribute__((aligned(16))) char lds[GEO::G * GROUP_BYTES];
-    __shared__ __attribute__((aligned(16))) char stage[PF ? CODES[CODE].n * sizeof(T) : 16];
     // Waves of a workgroup whose threads own two quarters' worth of indices (TM8192: 1024 threads,
     // quarters of 512) differ only in which quarter they start in: one wave-uniform branch
     // selects a body with all pi_k constants folded (the barriers inside both copies count
     // arrivals of the whole workgroup, whichever copy a wave runs).
     if constexpr (LDPC_QUARTER_SPECIALISE && GEO::G == 1 && GEO::NT == 2 * Q && Q >= 64) {
         if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < Q)
-            decode_ms_body<CODE, T, IPT, PF, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
+            decode_ms_body<CODE, T, IPT, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
         else
-            decode_ms_body<CODE, T, IPT, PF, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
+            decode_ms_body<CODE, T, IPT, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
     } else if constexpr (LDPC_QUARTER_SPECIALISE >= 2 && GEO::G == 1 && GEO::NT == 4 * Q && Q >= 64) {
         const int jw = __builtin_amdgcn_readfirstlane((int)threadIdx.x) / Q;
-        if (jw == 0) decode_ms_body<CODE, T, IPT, PF, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
-        else if (jw == 1) decode_ms_body<CODE, T, IPT, PF, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
-        else if (jw == 2) decode_ms_body<CODE, T, IPT, PF, LEAN, 2, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
-        else decode_ms_body<CODE, T, IPT, PF, LEAN, 3, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
+        if (jw == 0) decode_ms_body<CODE, T, IPT, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
+        else if (jw == 1) decode_ms_body<CODE, T, IPT, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
+        else if (jw == 2) decode_ms_body<CODE, T, IPT, LEAN, 2, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
+        else decode_ms_body<CODE, T, IPT, LEAN, 3, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
     } else {
-        decode_ms_body<CODE, T, IPT, PF, LEAN, -1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, stage, app);
+        decode_ms_body<CODE, T, IPT, LEAN, -1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
     }
 }
 
-template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM = selfcorr_med3<CODE, T>(), int NANPASS = 0>
+template <int CODE, class T, int IPT, int LEAN, int FORM = selfcorr_med3<CODE, T>(), int NANPASS = 0>
 __global__ void __launch_bounds__((Geometry<CODE, T, IPT>::WG), (min_waves_per_simd<CODE, T, IPT, LEAN>()))
 decode_ms_kernel(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                  uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                  uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k)
 {
-    decode_ms_kernel_main<CODE, T, IPT, PF, LEAN, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k);
+    decode_ms_kernel_main<CODE, T, IPT, LEAN, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k);
 }
 
 // The same kernel for the ONE-WORKGROUP launches of single-frame host calls (notify.hpp): two more arguments and a completion ticket
@@ -1820,26 +1178,26 @@ decode_ms_kernel(const T *__restrict__ llrs, uint8_t *__restrict__ output,
 // (profiles/r06_kbench/launch_floor.txt); built for the codes of up to 2 048 bits, where a synchronisation is a fifth of a call.
 template <int CODE> constexpr bool notify_kernel_built() { return CODES[CODE].n <= 2048; }
 
-template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM = selfcorr_med3<CODE, T>(), int NANPASS = 0>
+template <int CODE, class T, int IPT, int LEAN, int FORM = selfcorr_med3<CODE, T>(), int NANPASS = 0>
 __global__ void __launch_bounds__((Geometry<CODE, T, IPT>::WG), (min_waves_per_simd<CODE, T, IPT, LEAN>()))
 decode_ms_notify_kernel(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                         uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                         uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k,
                         uint32_t *notify, uint32_t notify_ticket)
 {
-    decode_ms_kernel_main<CODE, T, IPT, PF, LEAN, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k);
+    decode_ms_kernel_main<CODE, T, IPT, LEAN, FORM, NANPASS>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k);
     notify_done(notify, notify_ticket);
 }
 
 // The soft-output form of decode_ms_kernel (SOFT above): the marginals go to `app` as well.  A kernel of its own, so that the
 // hard-only kernels keep their argument list and code.
-template <int CODE, class T, int IPT, bool PF, int LEAN, int FORM = selfcorr_med3<CODE, T>(), int NANPASS = 0>
+template <int CODE, class T, int IPT, int LEAN, int FORM = selfcorr_med3<CODE, T>(), int NANPASS = 0>
 __global__ void __launch_bounds__((Geometry<CODE, T, IPT>::WG), (min_waves_per_simd<CODE, T, IPT, LEAN>()))
 soft_decode_ms_kernel(const T *__restrict__ llrs, T *__restrict__ app, uint8_t *__restrict__ output,
                       uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                       uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k)
 {
-    decode_ms_kernel_main<CODE, T, IPT, PF, LEAN, FORM, NANPASS, true>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim,
+    decode_ms_kernel_main<CODE, T, IPT, LEAN, FORM, NANPASS, true>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim,
                                                                       claim_k, app);
 }
 

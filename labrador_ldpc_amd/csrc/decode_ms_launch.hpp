@@ -146,10 +146,6 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
 {
     const bool static_stride = (lflags & LF_STATIC) != 0 || NANPASS == 2;     // (the second NaN pass walks its own stride classes)
     using GEO = Geometry<CODE, T, IPT>;
-    // LLR staging (PF) is implemented but measured SLOWER than plain loads at the start of each
-    // codeword on TM8192 (4.99 vs 5.29 M codewords/s: the extra live state costs spills at the
-    // 128-VGPR budget), so it stays off; see DESIGN.md section 7.
-    constexpr bool PF = false;
     if (batch == 0) return hipSuccess;
     const size_t groups = (batch + GEO::G - 1) / GEO::G;
     if (batch > 0xFFFFFFFFull || groups > 0x7FFFFFFFull) return hipErrorInvalidValue;   // (capi.hip slices larger batches)
@@ -159,8 +155,8 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
     // is a queue that costs no atomics (the TC codes' draws would hit the device's ceiling of ~85 M same-address atomics per
     // second: claim_chunk()).
     size_t resident;
-    if constexpr (SOFT) resident = resident_workgroups<soft_decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG>();
-    else resident = resident_workgroups<decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>, GEO::WG>();
+    if constexpr (SOFT) resident = resident_workgroups<soft_decode_ms_kernel<CODE, T, IPT, LEAN, FORM, NANPASS>, GEO::WG>();
+    else resident = resident_workgroups<decode_ms_kernel<CODE, T, IPT, LEAN, FORM, NANPASS>, GEO::WG>();
     constexpr bool queue_fed = GEO::WG >= 512;
     uint32_t *claim = (static_stride || maxiters == 0 || !queue_fed) ? nullptr : claim_counter(stream);
     // groups per draw: at least ~8 draws per resident workgroup, so that the last chunks are a small part of a short launch
@@ -175,20 +171,20 @@ hipError_t launch_cfg_form(const T *llrs, uint8_t *output, uint32_t *iters, uint
     }
     constexpr bool clamp_form = std::is_same_v<T, float> && FORM == 2;
     if constexpr (SOFT) {
-        hipLaunchKernelGGL((soft_decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>), dim3((unsigned)grid), dim3(GEO::WG), 0, stream,
+        hipLaunchKernelGGL((soft_decode_ms_kernel<CODE, T, IPT, LEAN, FORM, NANPASS>), dim3((unsigned)grid), dim3(GEO::WG), 0, stream,
                            llrs, app, output, iters, success, (uint32_t)batch, maxiters, nocap_limit_for(maxiters, clamp_form), claim, (uint32_t)K);
         return hipGetLastError();
     } else {
     if constexpr (NANPASS == 0 && notify_kernel_built<CODE>()) {        // (a two-pass decode is two launches: never)
         uint32_t *notify = nullptr, notify_ticket = 0;
         if (take_notify(grid, notify, notify_ticket)) {
-            hipLaunchKernelGGL((decode_ms_notify_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>), dim3(1), dim3(GEO::WG), 0, stream,
+            hipLaunchKernelGGL((decode_ms_notify_kernel<CODE, T, IPT, LEAN, FORM, NANPASS>), dim3(1), dim3(GEO::WG), 0, stream,
                                llrs, output, iters, success, (uint32_t)batch, maxiters, nocap_limit_for(maxiters, clamp_form), claim, (uint32_t)K,
                                notify, notify_ticket);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((decode_ms_kernel<CODE, T, IPT, PF, LEAN, FORM, NANPASS>), dim3((unsigned)grid), dim3(GEO::WG), 0, stream,
+    hipLaunchKernelGGL((decode_ms_kernel<CODE, T, IPT, LEAN, FORM, NANPASS>), dim3((unsigned)grid), dim3(GEO::WG), 0, stream,
                        llrs, output, iters, success, (uint32_t)batch, maxiters, nocap_limit_for(maxiters, clamp_form), claim, (uint32_t)K);
     return hipGetLastError();
     }
@@ -229,8 +225,8 @@ hipError_t launch_cfg(const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *
         constexpr int FORM = selfcorr_med3<CODE, T>();
         static_assert(!has_nocap_loop<CODE, T, IPT, LEAN>());
         int resident;
-        if constexpr (SOFT) resident = resident_workgroups<soft_decode_ms_kernel<CODE, T, IPT, false, LEAN, FORM, 1>, Geometry<CODE, T, IPT>::WG>();
-        else resident = resident_workgroups<decode_ms_kernel<CODE, T, IPT, false, LEAN, FORM, 1>, Geometry<CODE, T, IPT>::WG>();
+        if constexpr (SOFT) resident = resident_workgroups<soft_decode_ms_kernel<CODE, T, IPT, LEAN, FORM, 1>, Geometry<CODE, T, IPT>::WG>();
+        else resident = resident_workgroups<decode_ms_kernel<CODE, T, IPT, LEAN, FORM, 1>, Geometry<CODE, T, IPT>::WG>();
         bool two = batch >= 2 * (size_t)resident;
         if (lflags & LF_TWO_PASS) two = true;
         if ((lflags & LF_ONE_PASS) || maxiters == 0 || maxiters == NAN_MARK) two = false;

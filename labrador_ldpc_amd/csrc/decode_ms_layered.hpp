@@ -26,8 +26,8 @@
 // bit per variable, written by a ballot per wave and codeword (TM8192: 120 KB of u, 32 KB of LLRs and 1.25 KB of bits).
 #pragma once
 
-#include "decode_ms_kernel.hpp"
-#include "decode_ms_tables.hpp"
+#include "decode_ms_ops.hpp"         // Ops<float>, exclusive_min; static_for, row_block, pi_dev, LDPC_SYNC
+#include "decode_ms_tables.hpp"      // LDPC_TABLE_F32: the flooding default's indices per thread
 
 namespace ldpc {
 

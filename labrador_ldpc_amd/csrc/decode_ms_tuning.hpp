@@ -11,7 +11,7 @@
     defined(LDPC_PRIO_ROWS_LEAN) || defined(LDPC_PRIO_VAR) || defined(LDPC_TM2048_WAVES) || defined(LDPC_PAIR_LOCAL_IN_VAR) || defined(LDPC_PAIR_NOCAP) || \
     defined(LDPC_PAIR_ODD_B64) || defined(LDPC_PRIO_ROWS_PAIR) || defined(LDPC_SELFCORR_CARRY) || defined(LDPC_WAVE_VERDICT) || defined(LDPC_WG_VERDICT) || \
     defined(LDPC_PEEL_FIRST) || defined(LDPC_PAIR_PEEL_FIRST) || defined(LDPC_PAIR_FETCH_EARLY) || defined(LDPC_PAIR_SELFCORR_CARRY) || \
-    defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_VERDICT) || defined(LDPC_LEAN_CH)
+    defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH)
 #error "the LDPC_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/)"
 #endif
 #endif
@@ -28,7 +28,7 @@
 #define LDPC_SELFCORR_CARRY -1
 #endif
 // Self-correction as a clamp, v = med3(nv, 0, nv + old * big) (Ops<float>::clamp_to_side): -1 = per kernel
-// (selfcorr_med3()), 0 = off, 2 = v_fma form, 3 = v_mul_legacy form, 5 = three full-rate operations, no median.
+// (selfcorr_med3()), 0 = off, 2 = v_fma form, 3 = v_mul_legacy form (6, two full-rate operations and no median: integer messages only).
 #ifndef LDPC_SELFCORR_MED3
 #define LDPC_SELFCORR_MED3 -1
 #endif
@@ -60,11 +60,6 @@
 // the same for multi-wave codewords through a third barrier per iteration: -1 = per code and type (WG_VERDICT_SET)
 #ifndef LDPC_WG_VERDICT
 #define LDPC_WG_VERDICT -1
-#endif
-// register-lean kernels: in-phase verdict through a third barrier, skipping the minima / next-u half of the last check phase
-// (LEAN_VERDICT in the kernel body): -1 = per kernel (lean_verdict_default())
-#ifndef LDPC_LEAN_VERDICT
-#define LDPC_LEAN_VERDICT -1
 #endif
 // f32: clamp-free check phase for codewords whose LLRs are bounded (NOCAP_POSSIBLE in the kernel body).
 #ifndef LDPC_NOCAP

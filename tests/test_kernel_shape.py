@@ -232,7 +232,7 @@ def test_one_wave_f32_kernels_with_llrs_in_lds_fit_four_waves_per_simd(built_obj
     import kernel_resources
     seen = {}
     for obj, dem, v, sp, s, lds, scr in kernel_resources.resources("build/csrc/decode_ms_f32.o"):
-        m = __import__("re").search(r"decode_ms_kernel<(\d), float, 1, false, 0, ", dem)
+        m = __import__("re").search(r"decode_ms_kernel<(\d), float, 1, 0, ", dem)
         if m:
             seen.setdefault(int(m.group(1)), []).append((int(v), int(sp), int(lds)))
     assert set(seen) >= {0, 1, 2}

@@ -32,9 +32,6 @@
 #ifndef KPAIR
 #define KPAIR 0
 #endif
-#ifndef KPF
-#define KPF false
-#endif
 #ifndef KMAXIT
 #define KMAXIT 25
 #endif
@@ -66,7 +63,7 @@ int main()
         CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_pair_kernel<code, KT>, PairGeometry<code, KT>::NT, 0));
         const unsigned chunks = groups;
 #else
-        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_kernel<code, KT, KIPT, KPF, KLEAN, selfcorr_med3<code, KT>(), KNANPASS>, GEO::WG, 0));
+        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_ms_kernel<code, KT, KIPT, KLEAN, selfcorr_med3<code, KT>(), KNANPASS>, GEO::WG, 0));
 #ifdef KSTATIC
         const unsigned K = 1, chunks = groups;
 #else
@@ -101,7 +98,7 @@ int main()
 #if KPAIR
         hipLaunchKernelGGL((decode_ms_pair_kernel<code, KT>), dim3(groups), dim3(PairGeometry<code, KT>::NT), 0, 0, llrs, out, iters, ok, (uint32_t)F, (uint32_t)KMAXIT, KLIMIT, claim);
 #else
-        hipLaunchKernelGGL((decode_ms_kernel<code, KT, KIPT, KPF, KLEAN, selfcorr_med3<code, KT>(), KNANPASS>), dim3(groups), dim3(GEO::WG), 0, 0, llrs, out, iters, ok, (uint32_t)F, (uint32_t)KMAXIT, KLIMIT, claim, (uint32_t)claim_chunk<code, KT, KIPT>());
+        hipLaunchKernelGGL((decode_ms_kernel<code, KT, KIPT, KLEAN, selfcorr_med3<code, KT>(), KNANPASS>), dim3(groups), dim3(GEO::WG), 0, 0, llrs, out, iters, ok, (uint32_t)F, (uint32_t)KMAXIT, KLIMIT, claim, (uint32_t)claim_chunk<code, KT, KIPT>());
 #endif
         CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
         float ms; CK(hipEventElapsedTime(&ms, a, b));
@@ -190,7 +187,7 @@ int main()
     }
 #endif
     if (claim) { uint32_t left = 1; CK(hipMemcpy(&left, claim, 4, hipMemcpyDeviceToHost)); if (left != 0) printf("QUEUE HEAD NOT RESET: %u\n", left); }
-    printf("%scode %d T%zu ipt %d pf %d grid %u frames %zu: %.3f ms -> %.3f M cw/s | mean iters %.3f success %.5f | hash %016llx\n", KPAIR ? "PAIR " : "", code, sizeof(KT), KIPT, (int)KPF, groups, F, best,
+    printf("%scode %d T%zu ipt %d grid %u frames %zu: %.3f ms -> %.3f M cw/s | mean iters %.3f success %.5f | hash %016llx\n", KPAIR ? "PAIR " : "", code, sizeof(KT), KIPT, groups, F, best,
            F / best / 1e3, si / F, sk / F, h);
     return 0;
 }
