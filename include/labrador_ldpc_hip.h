@@ -347,10 +347,10 @@ int labrador_ldpc_decode_ms_soft_batch_f64(enum labrador_ldpc_code code, const d
                                            uint8_t *output, uint32_t *iters, uint8_t *success,
                                            size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
 
-/* Layered schedule (f32; for i8 and i16 LLRs see the fixed-point calls further down): block-row layered min-sum decoding instead of the reference's flooding schedule.  Block row r of the
- * prototype (a "layer": 4 for the TC codes, 3 for the TM codes) updates its checks from marginals that already hold the new messages of
- * rows 0 .. r-1 of the same sweep; a sweep is one pass over every layer, and the decode stops at the first sweep whose marginals
- * satisfy every check.  Same arithmetic as decode_ms::<f32> (plain IEEE adds and subtracts, self-correction, min-sum with the FLT_MAX
+/* Layered schedule (f32; for i8 and i16 LLRs see the fixed-point calls further down): block-row layered min-sum decoding instead
+ * of the reference's flooding schedule.  Block row r of the prototype (a "layer": 4 for the TC codes, 3 for the TM codes) updates
+ * its checks from marginals that already hold the new messages of rows 0 .. r-1 of the same sweep; a sweep is one pass over every
+ * layer, and the decode stops at the first sweep whose marginals satisfy every check.  Same arithmetic as decode_ms::<f32> (plain IEEE adds and subtracts, self-correction, min-sum with the FLT_MAX
  * cap); DESIGN.md 4.5 states the semantics the results are pinned to.  Not the reference's iteration trace: fewer sweeps than its
  * iterations, and a lower frame error rate at the same cap.
  *   output      hard decisions of the returned sweep's marginals, as labrador_ldpc_decode_ms_batch_f32;
@@ -368,9 +368,9 @@ int labrador_ldpc_decode_ms_layered_soft_batch_f32(enum labrador_ldpc_code code,
                                                    uint8_t *output, uint32_t *iters, uint8_t *success,
                                                    size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
 
-/* Layered schedule with normalized / offset min-sum (f32 only).  Plain min-sum overestimates the magnitude of a check
- * message; these calls are the two layered calls above with one step added.  Where a layer forms an edge's new message, its
- * magnitude m (min1 or min2 of the check, capped at FLT_MAX) becomes
+/* Layered schedule with normalized / offset min-sum (f32; the fixed-point calls have their own form further down).
+ * Plain min-sum overestimates the magnitude of a check message; these calls are the two layered calls above with one step added.
+ * Where a layer forms an edge's new message, its magnitude m (min1 or min2 of the check, capped at FLT_MAX) becomes
  *     t  = scale * m         one IEEE f32 multiply, rounded
  *     t  = t - offset        one IEEE f32 subtract, rounded (never fused with the multiply)
  *     m' = t > 0 ? t : +0.0
@@ -381,7 +381,9 @@ int labrador_ldpc_decode_ms_layered_soft_batch_f32(enum labrador_ldpc_code code,
  *   offset  0 <= offset <= FLT_MAX ("offset min-sum"), in the UNITS OF THE LLRS: a value that suits LLRs of the form +-1 + noise does
  *           not suit the same frames scaled by 2 / sigma^2, and a value that helps one code and noise level can hurt at another.
  * One pair per call.  A NaN, an infinity or a value outside these ranges returns LABRADOR_LDPC_HIP_EINVAL (the message names the
- * parameter), decided with the other argument checks before any device work.  With scale = 1 and offset = 0 the step is the identity
+ * parameter), decided with the other argument checks before any device work -- and before the batch is looked at, so an empty batch
+ * with a bad pair is refused too (the fixed-point calls further down check their triple after the buffers, and an empty batch
+ * returns OK whatever the triple).  With scale = 1 and offset = 0 the step is the identity
  * and the results equal those of the plain layered calls bit for bit, app included.  The library chooses no default: DESIGN.md 4.6
  * gives measured starting points.  Everything else as labrador_ldpc_decode_ms_layered_batch_f32 /
  * labrador_ldpc_decode_ms_layered_soft_batch_f32.  Returns a status code. */
@@ -417,6 +419,41 @@ int labrador_ldpc_decode_ms_layered_fixed_soft_batch_i8(enum labrador_ldpc_code 
 int labrador_ldpc_decode_ms_layered_fixed_soft_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, int32_t *app,
                                                          uint8_t *output, uint32_t *iters, uint8_t *success,
                                                          size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+
+/* Fixed-point layered schedule with normalized / offset min-sum (i8 and i16): the four calls above with one step
+ * added, in integers.  Where a layer forms an edge's new message, its magnitude m (min1 or min2 of the check, 0 <= m <= T_MAX) becomes
+ *     t  = (scale_num * m + ((1 << scale_shift) >> 1)) >> scale_shift      exact in 32 bits; ROUND HALF UP (scale_shift = 0 adds nothing)
+ *     m' = max(t - offset, 0)
+ * and the signs are applied to m' as they are to m, a zero m' included.  Which of min1 / min2 an edge takes is decided on the
+ * uncorrected values; everything else (the clamp of nv, self-correction, the exact int32 marginals, the stop rule, iters, success,
+ * output, the int32 app, max_iters = 0) is the fixed-point layered contract unchanged.
+ *   scale_shift  0 .. 8: the scale is the dyadic fraction scale_num / (1 << scale_shift);
+ *   scale_num    1 .. 1 << scale_shift (a scale in (0, 1]);
+ *   offset       0 .. T_MAX of the LLR type (127 / 32767), in the UNITS OF THE LLRS, which here are units of the caller's quantiser:
+ *                an offset that helps one code and noise level can hurt at another.
+ * One triple per call.  A value outside these ranges returns LABRADOR_LDPC_HIP_EINVAL (the message names the parameter), decided with
+ * the other argument checks, after the buffers and before any device work.  m' <= m, so every bound of the fixed-point contract
+ * holds.  (1 << k, k, 0) is the identity for every k: the results then equal those of the plain fixed-point calls bit for bit, app
+ * included.  The library chooses no default: DESIGN.md 4.8 gives measured starting points (13 / 16 for i8 at 8 / 31).  Everything
+ * else as the four calls above.  Returns a status code. */
+int labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, uint8_t *output,
+                                                             uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                             uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                             const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, uint8_t *output,
+                                                              uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                              uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                              const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app,
+                                                                  uint8_t *output, uint32_t *iters, uint8_t *success,
+                                                                  size_t batch, size_t max_iters, uint32_t scale_num,
+                                                                  uint32_t scale_shift, uint32_t offset,
+                                                                  const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, int32_t *app,
+                                                                   uint8_t *output, uint32_t *iters, uint8_t *success,
+                                                                   size_t batch, size_t max_iters, uint32_t scale_num,
+                                                                   uint32_t scale_shift, uint32_t offset,
+                                                                   const struct labrador_ldpc_hip_opts *opts);
 
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import enum
+import operator
 import os
 from typing import Optional, Tuple
 
@@ -86,6 +87,10 @@ SYMBOLS = {
                                                                         _optp]),
     **{f"labrador_ldpc_decode_ms_layered_fixed_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_layered_fixed_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("i8", "i16")},
+    **{f"labrador_ldpc_decode_ms_layered_fixed_corrected_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_uint32, _c.c_uint32,
+                                                                            _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    **{f"labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_uint32,
+                                                                                 _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -283,6 +288,21 @@ _SUBMATRIX = {0: (16, 16), 1: (32, 32), 2: (64, 64), 3: (128, 32), 4: (256, 64),
               6: (512, 128), 7: (1024, 256), 8: (2048, 512)}
 
 
+def _fixed_correction(scale_num, scale_shift, offset):
+    """The (scale_num, scale_shift, offset) of a corrected fixed-point layered call, or None when none of them is given (the plain
+    call).  The ranges are the library's to check; here only what ctypes would wrap into a uint32_t without a word is refused."""
+    if scale_num is None and scale_shift is None and offset is None:
+        return None
+    shift = operator.index(0 if scale_shift is None else scale_shift)
+    # (a scale_shift out of range is refused by the library before it looks at scale_num: the default only has to exist)
+    triple = (operator.index(1 << min(max(shift, 0), 8) if scale_num is None else scale_num), shift,
+              operator.index(0 if offset is None else offset))
+    for name, v in zip(("scale_num", "scale_shift", "offset"), triple):
+        if not 0 <= v < 1 << 32:
+            raise ValueError(f"{name} does not fit a uint32_t")
+    return triple
+
+
 class LDPCCode(enum.IntEnum):
     """`enum LDPCCode` (src/codes/mod.rs:37-66) with the crate's method names."""
 
@@ -429,22 +449,40 @@ class LDPCCode(enum.IntEnum):
                                 stream, devices, extra=(float(scale), float(offset)))
 
     def decode_ms_layered_fixed_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
-                                      variant: int = 0, stream: Optional[int] = None, devices=None):
+                                      variant: int = 0, stream: Optional[int] = None, devices=None,
+                                      scale_num: Optional[int] = None, scale_shift: Optional[int] = None, offset: Optional[int] = None):
         """The block-row layered schedule in FIXED POINT, for int8 and int16 LLRs (labrador_ldpc_decode_ms_layered_fixed_batch_i8 /
         _i16).  A contract of its own: marginals are exact int32 sums, the only saturation is the clamp of a new
         variable message to +-T_MAX (127 / 32767), and an LLR equal to the type's minimum is read as -T_MAX.  `iters` counts sweeps
         as decode_ms_layered_batch does.  Buffers, `stream` and `devices` as decode_ms_batch; `variant` 0 is the only kernel.
-        Returns (output, iters, success)."""
-        return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_batch_", llrs, maxiters, output, iters, success, variant, stream,
-                                devices)
+        Returns (output, iters, success).
+
+        `scale_num`, `scale_shift`, `offset`: normalized / offset min-sum in integers
+        (labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8 / _i16) -- every check message magnitude m becomes
+        max(((scale_num * m + ((1 << scale_shift) >> 1)) >> scale_shift) - offset, 0): the scale scale_num / 2^scale_shift in (0, 1]
+        with 0 <= scale_shift <= 8, rounded half up, then an offset of 0 .. T_MAX in the units of the quantised LLRs.  The library
+        checks the ranges (LdpcHipError).  With none of the three given the call is plain min-sum through the plain entry point; with
+        any of them given, the others default to scale_num = 1 << scale_shift, scale_shift = 0 and offset = 0."""
+        extra = _fixed_correction(scale_num, scale_shift, offset)
+        if extra is None:
+            return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_batch_", llrs, maxiters, output, iters, success, variant,
+                                    stream, devices)
+        return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_corrected_batch_", llrs, maxiters, output, iters, success, variant,
+                                stream, devices, extra=extra)
 
     def decode_ms_layered_fixed_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
-                                           variant: int = 0, stream: Optional[int] = None, devices=None):
+                                           variant: int = 0, stream: Optional[int] = None, devices=None,
+                                           scale_num: Optional[int] = None, scale_shift: Optional[int] = None, offset: Optional[int] = None):
         """decode_ms_layered_fixed_batch with soft output (labrador_ldpc_decode_ms_layered_fixed_soft_batch_i8 / _i16): also the
         marginals of the returned sweep, ALWAYS int32 whatever the LLR type.  Returns (app[batch, n + p] int32, output, iters,
-        success)."""
-        return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_soft_batch_", llrs, maxiters, output, iters, success, variant,
-                                stream, devices, soft=True, app=app, app_dtype="i32")
+        success).  `scale_num`, `scale_shift` and `offset` as decode_ms_layered_fixed_batch
+        (labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_i8 / _i16)."""
+        extra = _fixed_correction(scale_num, scale_shift, offset)
+        if extra is None:
+            return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_soft_batch_", llrs, maxiters, output, iters, success, variant,
+                                    stream, devices, soft=True, app=app, app_dtype="i32")
+        return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_", llrs, maxiters, output, iters, success,
+                                variant, stream, devices, soft=True, app=app, app_dtype="i32", extra=extra)
 
     def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=(),
                     app_dtype=None):

@@ -80,10 +80,18 @@ LDPC_DEV int bit_mask(uint32_t w)
     return (int)(w << (31 - J)) >> 31;
 }
 
-template <int CODE, class T, bool SOFT>
+// CORRECTED: normalized / offset min-sum in integers -- every message magnitude m becomes
+//     max(((scale_num * m + ((1 << scale_shift) >> 1)) >> scale_shift) - offset, 0)              (round half up, then the offset)
+// with 0 <= scale_shift <= 8, 1 <= scale_num <= 1 << scale_shift and 0 <= offset <= T_MAX, checked by capi.hip: the product is at
+// most 256 * 32767 + 128 and the result at most m.  A check is held as its two minima, so the step is taken ONCE PER CHECK, on min1
+// and min2 as they go into the registers -- the minima themselves were taken on the uncorrected |v| -- and every message of the check
+// is built from the corrected pair, now (u_new) and on the next visit (u_old); equal minima correct to equal values, so a tie stays
+// harmless.  The three parameters are wave-uniform kernel arguments; without CORRECTED they are not read.
+template <int CODE, class T, bool SOFT, bool CORRECTED = false>
 LDPC_DEV void decode_ms_layered_fixed_body(const T *__restrict__ llrs, int32_t *__restrict__ app, uint8_t *__restrict__ output,
                                            uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out, uint32_t batch,
-                                           uint32_t maxiters, uint32_t *claim, char *lds)
+                                           uint32_t maxiters, uint32_t *claim, char *lds, uint32_t scale_num = 1, uint32_t scale_shift = 0,
+                                           uint32_t offset = 0)
 {
     using GEO = LayeredFixedGeometry<CODE>;
     constexpr Prototype P = GEO::P;
@@ -189,7 +197,16 @@ LDPC_DEV void decode_ms_layered_fixed_body(const T *__restrict__ llrs, int32_t *
                             n_zr |= (a < 1u ? 1u : 0u) << j;
                         });
                         n_sg = r_sg & ~drop & DMASK;
-                        const int n_m1 = (int)(k1 >> 5), n_m2 = (int)(k2 >> 5), n_pos = (int)(k1 & 31u);
+                        int n_m1 = (int)(k1 >> 5), n_m2 = (int)(k2 >> 5);
+                        const int n_pos = (int)(k1 & 31u);
+                        if constexpr (CORRECTED) {
+                            // (a multiply, an add, a shift, a subtract and a max, twice per check)
+                            const uint32_t half = (1u << scale_shift) >> 1;
+                            const int t1 = (int)((scale_num * (uint32_t)n_m1 + half) >> scale_shift) - (int)offset;
+                            const int t2 = (int)((scale_num * (uint32_t)n_m2 + half) >> scale_shift) - (int)offset;
+                            n_m1 = t1 > 0 ? t1 : 0;
+                            n_m2 = t2 > 0 ? t2 : 0;
+                        }
                         const uint32_t n_neg = n_sg ^ (0u - (uint32_t)(__builtin_popcount(n_sg) & 1));
                         mn[q][r] = (uint32_t)n_m1 | ((uint32_t)n_m2 << 16);
                         sg[q][r] = n_sg | ((uint32_t)n_pos << 27);
@@ -292,6 +309,19 @@ decode_ms_layered_fixed_kernel(const T *__restrict__ llrs, int32_t *__restrict__
 {
     __shared__ __attribute__((aligned(16))) char lds[LayeredFixedGeometry<CODE>::LDS_BYTES];
     decode_ms_layered_fixed_body<CODE, T, SOFT>(llrs, app, output, iters_out, success_out, batch, maxiters, claim, lds);
+}
+
+// The same body with the correction step, as kernels of their own (decode_ms_fixed_corrected.hip): the plain kernels above keep
+// their symbols, their arguments and their instructions.
+template <int CODE, class T, bool SOFT>
+__global__ void __launch_bounds__(LayeredFixedGeometry<CODE>::WG)
+decode_ms_layered_fixed_corrected_kernel(const T *__restrict__ llrs, int32_t *__restrict__ app, uint8_t *__restrict__ output,
+                                         uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out, uint32_t batch,
+                                         uint32_t maxiters, uint32_t *claim, uint32_t scale_num, uint32_t scale_shift, uint32_t offset)
+{
+    __shared__ __attribute__((aligned(16))) char lds[LayeredFixedGeometry<CODE>::LDS_BYTES];
+    decode_ms_layered_fixed_body<CODE, T, SOFT, true>(llrs, app, output, iters_out, success_out, batch, maxiters, claim, lds, scale_num,
+                                                      scale_shift, offset);
 }
 
 }  // namespace ldpc

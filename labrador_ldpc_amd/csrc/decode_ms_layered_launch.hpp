@@ -1,5 +1,6 @@
 // decode_ms_layered_launch.hpp -- the host side that the layered launchers share (decode_ms_layered_f32.hip, decode_ms_corrected_f32.hip,
-// decode_ms_fixed_layered.hip): the persistent launch of one kernel, and the dispatch from (code, variant, app) to it.
+// decode_ms_fixed_layered.hip, decode_ms_fixed_corrected.hip): the persistent launch of one kernel, and the dispatch from (code,
+// variant, app) to it.
 #pragma once
 
 #include "decode_ms_launch.hpp"          // claim_counter, persistent_grid, resident_workgroups, LDPC_TABLE_F32

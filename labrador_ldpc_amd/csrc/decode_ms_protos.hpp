@@ -39,5 +39,12 @@ hipError_t launch_decode_ms_layered_corrected(int code, int variant, const float
 template <class T>
 hipError_t launch_decode_ms_layered_fixed(int code, int variant, const T *llrs, int32_t *app, uint8_t *output, uint32_t *iters,
                                           uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream);
+// ... in fixed point with normalized / offset check messages (decode_ms_fixed_corrected.hip): every message magnitude m becomes
+// max(((scale_num * m + ((1 << scale_shift) >> 1)) >> scale_shift) - offset, 0); the three are the caller's, already range-checked
+// (capi.hip)
+template <class T>
+hipError_t launch_decode_ms_layered_fixed_corrected(int code, int variant, const T *llrs, int32_t *app, uint8_t *output, uint32_t *iters,
+                                                    uint8_t *success, size_t batch, uint32_t maxiters, uint32_t scale_num,
+                                                    uint32_t scale_shift, uint32_t offset, hipStream_t stream);
 
 }  // namespace ldpc

@@ -12,7 +12,9 @@ from the same frames; the default, flooding, is the reference's decoder and keep
 DESIGN.md 4.6); `--offset` is in the units of the LLRs, which here are +-1 + noise.  `--llr i8` / `--llr i16` (layered schedule only)
 quantise the frames on the device -- labrador_ldpc_hip_awgn_i8's clamp(rint(`--llr-scale` * y), +-`--llr-lim`), widened for i16 --
 and decode them with the fixed-point layered decoder (labrador_ldpc_decode_ms_layered_fixed_batch_i8 / _i16); f32 is
-the default and leaves everything else as it was.
+the default and leaves everything else as it was.  `--fixed-scale NUM/DEN` / `--fixed-offset INT` (with `--llr i8` / `i16` only) decode
+those frames with normalized / offset check messages in integers (labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8 / _i16,
+DESIGN.md 4.8): DEN is a power of two of at most 256, and the offset is in units of the quantiser.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -36,11 +38,14 @@ def sigma_for(code, snr_db: float, noise: str) -> float:
 
 def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100, batch: int = 65536,
               max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding",
-              scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31):
+              scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31,
+              scale_num=None, scale_shift=None, fixed_offset=None):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
     min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
-    fixed-point layered decoder on frames quantised as clamp(rint(llr_scale * y), +-llr_lim) (layered schedule, no correction)."""
+    fixed-point layered decoder on frames quantised as clamp(rint(llr_scale * y), +-llr_lim) (layered schedule, no float correction).
+    `scale_num`, `scale_shift`, `fixed_offset`: the fixed-point decoder's integer correction (decode_ms_layered_fixed_batch's
+    scale_num, scale_shift and offset; quantised LLRs only; None, the default, is plain min-sum)."""
     if schedule not in ("flooding", "layered"):
         raise ValueError(f"unknown schedule {schedule!r}")
     if schedule != "layered" and (scale != 1.0 or offset != 0.0):
@@ -49,6 +54,8 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         raise ValueError(f"unknown LLR type {llr!r}")
     if llr != "f32" and (schedule != "layered" or scale != 1.0 or offset != 0.0):
         raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
+    if llr == "f32" and not (scale_num is None and scale_shift is None and fixed_offset is None):
+        raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
     import torch
     dev = torch.device("cuda", device)
     k8 = code.k() // 8
@@ -63,7 +70,8 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         cw = code.encode_batch(data)                                         # perftest/src/main.rs:10-12
         if llr != "f32":                                                     # the same noise, quantised by the i8 channel kernel
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
-            out, _, _ = code.decode_ms_layered_fixed_batch(llrs if llr == "i8" else llrs.to(torch.int16), maxiters)
+            out, _, _ = code.decode_ms_layered_fixed_batch(llrs if llr == "i8" else llrs.to(torch.int16), maxiters,
+                                                           scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset)
         else:
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
             if schedule == "layered":
@@ -79,6 +87,17 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     bits = trials * code.k()
     ber = max(1, errors) / bits                                              # :59-61
     return trials, bits, errors, ber, frame_errors
+
+
+def fixed_scale(text: str):
+    """`NUM/DEN` -> (scale_num, scale_shift): DEN a power of two of at most 256, 1 <= NUM <= DEN."""
+    try:
+        num, den = (int(x) for x in text.split("/"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not NUM/DEN")
+    if den < 1 or den > 256 or den & (den - 1) or not 1 <= num <= den:
+        raise argparse.ArgumentTypeError(f"{text!r}: DEN must be a power of two of at most 256 and 1 <= NUM <= DEN")
+    return num, den.bit_length() - 1
 
 
 def main(argv=None):
@@ -98,17 +117,27 @@ def main(argv=None):
                     help="LLR type; i8 / i16: the fixed-point layered decoder on quantised frames (--schedule layered)")
     ap.add_argument("--llr-scale", type=float, default=8.0, help="quantiser: clamp(rint(scale * y), +-lim) (--llr i8 / i16)")
     ap.add_argument("--llr-lim", type=int, default=31, help="quantiser limit, at most 127 (--llr i8 / i16)")
+    ap.add_argument("--fixed-scale", type=fixed_scale, default=None, metavar="NUM/DEN",
+                    help="fixed-point normalized min-sum factor, DEN a power of two of at most 256 (--llr i8 / i16)")
+    ap.add_argument("--fixed-offset", type=int, default=None, metavar="INT",
+                    help="fixed-point offset min-sum term in units of the quantiser, >= 0 (--llr i8 / i16)")
     args = ap.parse_args(argv)
     if args.schedule != "layered" and (args.scale != 1.0 or args.offset != 0.0):
         ap.error("--scale and --offset need --schedule layered")
     if args.llr != "f32" and (args.schedule != "layered" or args.scale != 1.0 or args.offset != 0.0):
         ap.error("--llr i8 / i16 needs --schedule layered without --scale and --offset")
+    if args.llr == "f32" and (args.fixed_scale is not None or args.fixed_offset is not None):
+        ap.error("--fixed-scale and --fixed-offset need --schedule layered --llr i8 / i16")
+    if args.fixed_offset is not None and args.fixed_offset < 0:
+        ap.error("--fixed-offset must be >= 0")
+    scale_num, scale_shift = args.fixed_scale if args.fixed_scale is not None else (None, None)
     code = LDPCCode[args.code]
     for snr in (float(x) for x in args.snrs.split(",")):
         trials, bits, errors, ber, fe = ms_trials(code, snr, args.noise, args.maxiters, args.batch,
                                                   args.max_bits, args.max_errors, schedule=args.schedule,
                                                   scale=args.scale, offset=args.offset, llr=args.llr,
-                                                  llr_scale=args.llr_scale, llr_lim=args.llr_lim)
+                                                  llr_scale=args.llr_scale, llr_lim=args.llr_lim, scale_num=scale_num,
+                                                  scale_shift=scale_shift, fixed_offset=args.fixed_offset)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 

@@ -8,14 +8,17 @@ Decoders (default: all):
                                                           symbol itself, since the Python keywords route (1, 0) to the plain entry
     flooding_i8                                           labrador_ldpc_decode_ms_batch_i8
     fixed_i8, fixed_i16                                   labrador_ldpc_decode_ms_layered_fixed_batch_i8 / _i16
+    fixed_i8_16_4_0, fixed_i8_13_4_0, fixed_i8_16_4_1     labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8 at that (scale_num,
+                                                          scale_shift, offset), on the i8 frames
 The f32 frames are awgn_frames(dtype="f32"); the i8 frames are the i8 channel kernel's quantisation (8 / 31) of the same job seed, and
 the i16 frames are those widened.  Passes: a flooding decode that succeeds at iteration index i made i passes, a layered one at sweep
 index i made i + 1; a failure counts as 25.  Cases: TC512 3 dB, TM2048 1.7 and 2 dB, TM8192 2 dB.  Default 1 048 576
 frames per case (TM8192: a quarter of that) and 5 repetitions.
 Per decoder: `mcw_s` (M codewords/s, the best repetition), `mcw_s_reps`, `spread` ((max - min) / max of the repetitions: what a
 difference has to exceed), `mean_passes`, `failures`, `fer`.  Per case: `unit_equals_layered` (corrected (1, 0) makes exactly the sweeps
-of plain layered decoding, so its ratio is the price of the added instructions and kernel arguments alone), every decoder's rate
-`_over_layered_f32`, and every layered decoder's over its flooding counterpart's."""
+of plain layered decoding, so its ratio is the price of the added instructions and kernel arguments alone), `identity_equals_fixed` (the
+same for fixed_i8_16_4_0 against fixed_i8), every decoder's rate `_over_layered_f32`, every layered decoder's over its flooding
+counterpart's, and every corrected fixed decoder's `_over_fixed_i8`."""
 import argparse
 import ctypes
 import json
@@ -32,9 +35,11 @@ from labrador_ldpc_amd import LDPCCode
 MAXITERS = 25
 CASES = (("TC512", 3.0), ("TM2048", 1.7), ("TM2048", 2.0), ("TM8192", 2.0))
 CORRECTED = {"corrected_1_0": (1.0, 0.0), "corrected_0.8125_0": (0.8125, 0.0), "corrected_1_0.1": (1.0, 0.1)}
+FIXED_CORRECTED = {"fixed_i8_16_4_0": (16, 4, 0), "fixed_i8_13_4_0": (13, 4, 0), "fixed_i8_16_4_1": (16, 4, 1)}
 # decoder -> (its frames, its flooding counterpart; None: it is a flooding decoder)
 DECODERS = {"flooding_f32": ("f32", None), "layered_f32": ("f32", "flooding_f32"), **{k: ("f32", "flooding_f32") for k in CORRECTED},
-            "flooding_i8": ("i8", None), "fixed_i8": ("i8", "flooding_i8"), "fixed_i16": ("i16", "flooding_i8")}
+            "flooding_i8": ("i8", None), "fixed_i8": ("i8", "flooding_i8"), "fixed_i16": ("i16", "flooding_i8"),
+            **{k: ("i8", "flooding_i8") for k in FIXED_CORRECTED}}
 
 
 def corrected_call(code, llrs, out, it, ok, scale, offset):
@@ -83,6 +88,10 @@ def main():
             x = llrs[DECODERS[k][0]]
             if k in CORRECTED:
                 return lambda: corrected_call(code, x, out[k], it[k], ok[k], *CORRECTED[k])
+            if k in FIXED_CORRECTED:
+                num, shift, offset = FIXED_CORRECTED[k]
+                return lambda: code.decode_ms_layered_fixed_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], scale_num=num,
+                                                                  scale_shift=shift, offset=offset)
             method = (code.decode_ms_batch if DECODERS[k][1] is None else
                       code.decode_ms_layered_batch if k == "layered_f32" else code.decode_ms_layered_fixed_batch)
             return lambda: method(x, MAXITERS, output=out[k], iters=it[k], success=ok[k])
@@ -102,6 +111,8 @@ def main():
         case = {"code": name, "ebn0_db": ebn0, "frames": frames}
         if "layered_f32" in keys and "corrected_1_0" in keys:
             case["unit_equals_layered"] = all(torch.equal(x["layered_f32"], x["corrected_1_0"]) for x in (out, it, ok))
+        if "fixed_i8" in keys and "fixed_i8_16_4_0" in keys:
+            case["identity_equals_fixed"] = all(torch.equal(x["fixed_i8"], x["fixed_i8_16_4_0"]) for x in (out, it, ok))
         for key in keys:
             succ = ok[key].to(torch.int64)
             passes = torch.where(succ == 1, it[key].to(torch.int64) + (0 if DECODERS[key][1] is None else 1), torch.full_like(succ, MAXITERS))
@@ -111,7 +122,7 @@ def main():
                          "mean_passes": round(float(passes.double().mean()), 3), "failures": int((succ == 0).sum()),
                          "fer": float(1.0 - succ.double().mean())}
         for key in keys:
-            for base in ("layered_f32", DECODERS[key][1]):
+            for base in ("layered_f32", DECODERS[key][1], "fixed_i8" if key in FIXED_CORRECTED else None):
                 if base in keys and base != key:
                     case[f"{key}_over_{base}"] = round(case[key]["mcw_s"] / case[base]["mcw_s"], 4)
         res["cases"].append(case)
