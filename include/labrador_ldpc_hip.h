@@ -455,6 +455,41 @@ int labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_i16(enum labrador
                                                                    uint32_t scale_shift, uint32_t offset,
                                                                    const struct labrador_ldpc_hip_opts *opts);
 
+/* Two-stage ("cascade") decoding: the flooding decoder first, the layered decoder on the frames it fails.  Per frame
+ * f, exactly, as a composition of the entry points above:
+ *     (o1, i1, s1) = labrador_ldpc_decode_ms_batch_<T> on frame f at cap max_iters, kernel opts->variant
+ *     if s1:  output, iters, success, stage = o1, i1, 1, 0
+ *     else:   (o2, i2, s2) = f32:      labrador_ldpc_decode_ms_layered_corrected_batch_f32 at (scale, offset)
+ *                            i8 / i16: labrador_ldpc_decode_ms_layered_fixed_corrected_batch_<T> at (scale_num, scale_shift, offset)
+ *                            on the ORIGINAL LLRs of frame f at cap max_sweeps, variant 0
+ *             output, iters, success, stage = o2, i2, s2, 1
+ *   stage   [batch]   which stage's results the frame carries: 0 = flooding, 1 = layered
+ *   iters   [batch]   in that stage's own unit: the flooding decoder's 0-based iteration index, or the layered sweep index
+ * A frame both stages fail carries stage 2's results: its last sweep's hard bits, iters = max_sweeps, success = 0.  max_iters = 0
+ * sends every frame to stage 2 (the layered entry's results, stage all 1); max_sweeps = 0 gives every frame stage 1 failed the
+ * layered entry's own answer to max_iters = 0: zero output, iters 0, success 0.  (1, 0) and (1 << k, k, 0) are the identity
+ * corrections: plain layered min-sum.  `opts->variant` chooses the stage-1 kernel as in labrador_ldpc_decode_ms_batch_*; stage 2
+ * has one kernel.  Hard output only.
+ * Arguments are checked in this order, all before any device work: `code`; for f32 the range of (scale, offset); an empty batch is
+ * OK whatever the pointers; a NULL buffer, `stage` included, is EINVAL; for i8 / i16 the ranges of the triple.  With MEM_DEVICE
+ * `output` must be 8-byte aligned; `llrs` need only be aligned to its element (a 16-byte aligned `llrs` is gathered faster).
+ * With MEM_DEVICE the call is NOT purely asynchronous: it waits on opts->stream once per launch slice (2^30 frames) for the number
+ * of frames stage 1 failed, and returns with the last slice's stage 2 and the copy of its results enqueued on that stream, so the
+ * results are valid once the stream is synchronised, as for every other MEM_DEVICE call.  It must not be called on a stream that
+ * is being captured into a graph.  Everything else (host buffers, device sets) as labrador_ldpc_decode_ms_batch_*.  Returns a
+ * status code. */
+int labrador_ldpc_decode_ms_cascade_batch_f32(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                              uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters, size_t max_sweeps,
+                                              float scale, float offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_batch_i8 (enum labrador_ldpc_code code, const int8_t *llrs, uint8_t *output, uint32_t *iters,
+                                              uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters, size_t max_sweeps,
+                                              uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                              const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, uint8_t *output, uint32_t *iters,
+                                              uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters, size_t max_sweeps,
+                                              uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                              const struct labrador_ldpc_hip_opts *opts);
+
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --
  * llrs[i], output[i] (8-byte aligned), iters[i], success[i], laid out as in labrador_ldpc_decode_ms_batch_* -- are DEVICE memory

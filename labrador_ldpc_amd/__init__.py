@@ -91,6 +91,9 @@ SYMBOLS = {
                                                                             _c.c_uint32, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_uint32,
                                                                                  _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    "labrador_ldpc_decode_ms_cascade_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _c.c_float, _optp]),
+    **{f"labrador_ldpc_decode_ms_cascade_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32, _c.c_uint32,
+                                                             _c.c_uint32, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -484,18 +487,43 @@ class LDPCCode(enum.IntEnum):
         return self._batch_call("labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_", llrs, maxiters, output, iters, success,
                                 variant, stream, devices, soft=True, app=app, app_dtype="i32", extra=extra)
 
+    def decode_ms_cascade_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, output=None, iters=None, success=None,
+                                stage=None, variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0,
+                                offset: float = 0.0):
+        """Two-stage decoding of f32 LLRs (labrador_ldpc_decode_ms_cascade_batch_f32): decode_ms_batch at cap
+        `maxiters` and kernel `variant`, then decode_ms_layered_batch at cap `max_sweeps` (None = `maxiters`) and (`scale`,
+        `offset`) on the original LLRs of the frames the first stage failed.  `stage[batch]` u8 says whose results a frame carries
+        (0 = flooding, 1 = layered) and `iters` is in that stage's unit.  Buffers, `stream` and `devices` as decode_ms_batch, but
+        with device buffers the call waits on the stream once for the first stage before it returns with the second enqueued.
+        Returns (output, iters, success, stage)."""
+        return self._batch_call("labrador_ldpc_decode_ms_cascade_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
+                                extra=(maxiters if max_sweeps is None else max_sweeps, float(scale), float(offset)), stage=stage,
+                                with_stage=True, types=("f32",))
+
+    def decode_ms_cascade_fixed_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, output=None, iters=None,
+                                      success=None, stage=None, variant: int = 0, stream: Optional[int] = None, devices=None,
+                                      scale_num: Optional[int] = None, scale_shift: Optional[int] = None, offset: Optional[int] = None):
+        """decode_ms_cascade_batch for int8 and int16 LLRs (labrador_ldpc_decode_ms_cascade_batch_i8 / _i16): the second stage is
+        decode_ms_layered_fixed_batch with its `scale_num`, `scale_shift` and `offset` (none given: plain min-sum)."""
+        return self._batch_call("labrador_ldpc_decode_ms_cascade_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
+                                extra=(maxiters if max_sweeps is None else max_sweeps,
+                                       *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0))), stage=stage, with_stage=True,
+                                types=("i8", "i16"))
+
     def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=(),
-                    app_dtype=None):
+                    app_dtype=None, with_stage=False, stage=None, types=None):
         # soft: the call also writes the marginals to `app` [batch, n + p], which comes back first
         # app_dtype: the dtype of `app` as a suffix ("i32"); None = the dtype of `llrs`
         # extra: arguments of the entry point between max_iters and opts
+        # with_stage: the call also writes `stage` [batch] u8, which comes back last
+        # types: the LLR types (suffixes) this method takes where the prefix has entries for more; None = whatever the prefix has
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
         if llrs.ndim != 2 or llrs.shape[1] != self.n():
             raise ValueError("llrs must be [batch, n]")
         batch, np_len = llrs.shape[0], self.n() + self.punctured_bits()
         try:
-            fn = getattr(lib, prefix + _suffix(llrs), None)
+            fn = getattr(lib, prefix + _suffix(llrs), None) if types is None or _suffix(llrs) in types else None
         except KeyError:
             fn = None
         if fn is None:
@@ -519,6 +547,8 @@ class LDPCCode(enum.IntEnum):
         iters = _result_buffer(iters, llrs, (batch,), "i32", "iters")
         success = _result_buffer(success, llrs, (batch,), "u8", "success")
         results = (app, output, iters, success) if soft else (output, iters, success)
+        if with_stage:
+            results += (_result_buffer(stage, llrs, (batch,), "u8", "stage"),)
         _check(fn(int(self), _ptr(llrs), *(_ptr(r) for r in results), batch, maxiters, *extra, ctypes.byref(opts)))
         del keep
         return results

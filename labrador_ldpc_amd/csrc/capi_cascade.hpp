@@ -1,0 +1,126 @@
+// capi_cascade.hpp -- part of capi.hip: the workspace of the cascade decode (labrador_ldpc_decode_ms_cascade_batch_*)
+// and what it does with one launch slice.
+#pragma once
+
+namespace {
+
+// failed frames per stage-2 launch: what fits 256 MiB of gathered LLRs, at least 8192 (every code's 8192 rows fit 256 MiB, so a
+// chunk's bytes and pieces always fit 32 bits).  LABRADOR_LDPC_HIP_CASCADE_CHUNK=<frames> lowers it, for tests.
+size_t cascade_chunk_frames(size_t llr_row_bytes)
+{
+    size_t c = ((size_t)256 << 20) / llr_row_bytes;
+    if (c < 8192) c = 8192;
+    if (const char *env = std::getenv("LABRADOR_LDPC_HIP_CASCADE_CHUNK")) {
+        const long long v = std::atoll(env);
+        if (v > 0 && (size_t)v < c) c = (size_t)v;
+    }
+    return c;
+}
+
+// Device memory between the two stages, grow-only, per calling thread and per device like StagingPool: `index` holds the counter
+// and the list of failed frames of a slice, `data` a chunk's gathered LLRs and dense stage-2 results.  Calls of one thread may use
+// different streams: `last_use` is recorded on a call's stream behind its last use of the workspace, and the next call makes its
+// own stream wait for it before it touches the workspace.  The count comes back through a pinned word, read after the call's own
+// synchronisation, so it needs no such care.
+struct CascadeWorkspace {
+    struct Block { void *p = nullptr; size_t cap = 0; };
+    Block index, data;
+    uint32_t *count_host = nullptr;
+    hipEvent_t last_use = nullptr;
+    bool pending = false;                          // last_use has been recorded since the workspace was (re)made
+    int dev = -1;
+    void drop()
+    {
+        if (dev < 0) return;
+        if (pending) (void)hipEventSynchronize(last_use);
+        for (Block *b : {&index, &data}) {
+            if (b->p) (void)hipFree(b->p);
+            *b = Block{};
+        }
+        (void)hipEventDestroy(last_use);
+        (void)hipHostFree(count_host);
+        last_use = nullptr; count_host = nullptr; pending = false; dev = -1;
+    }
+    ~CascadeWorkspace() { drop(); }
+    hipError_t ensure()
+    {
+        int cur = 0;
+        hipError_t e = hipGetDevice(&cur);
+        if (e != hipSuccess) return e;
+        if (dev == cur) return hipSuccess;
+        drop();
+        if ((e = hipEventCreateWithFlags(&last_use, hipEventDisableTiming)) != hipSuccess) return e;
+        if ((e = hipHostMalloc((void **)&count_host, 64, hipHostMallocDefault)) != hipSuccess) {
+            (void)hipEventDestroy(last_use);
+            last_use = nullptr; count_host = nullptr;
+            return e;
+        }
+        dev = cur;
+        return hipSuccess;
+    }
+    hipError_t reserve(Block &b, size_t bytes)
+    {
+        if (b.cap >= bytes) return hipSuccess;
+        if (b.p) {
+            if (pending) (void)hipEventSynchronize(last_use);       // an earlier call's work, maybe on another stream, may still use it
+            (void)hipFree(b.p);
+            b = Block{};
+        }
+        const hipError_t e = hipMalloc(&b.p, bytes);
+        if (e != hipSuccess) { b.p = nullptr; return e; }
+        b.cap = bytes;
+        return hipSuccess;
+    }
+};
+thread_local CascadeWorkspace g_cascade;
+
+// One launch slice of the cascade: stage 1 on every frame, the list of the frames it failed, their count read back (the one
+// synchronisation of `stream`), then gather, stage 2 and scatter in chunks of the failed frames.  stage1(llrs, output, iters,
+// success, frames, stream) and stage2(dense llrs, dense output, dense iters, dense success, frames, stream) enqueue the two decoders.
+template <class T, class Stage1, class Stage2>
+hipError_t cascade_slice(const ldpc::CodeInfo &ci, const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
+                         size_t nb, hipStream_t stream, const Stage1 &stage1, const Stage2 &stage2)
+{
+    if (hipError_t e = stage1(llrs, output, iters, success, nb, stream); e != hipSuccess) return e;
+    CascadeWorkspace &ws = g_cascade;
+    if (hipError_t e = ws.ensure(); e != hipSuccess) return e;
+    constexpr size_t LIST_AT = 16;                                  // the counter's word, then the list
+    if (hipError_t e = ws.reserve(ws.index, LIST_AT + nb * sizeof(uint32_t)); e != hipSuccess) return e;
+    if (ws.pending)
+        if (hipError_t e = hipStreamWaitEvent(stream, ws.last_use, 0); e != hipSuccess) return e;
+    struct Mark {                                                   // whatever was enqueued below, the next call waits for it
+        CascadeWorkspace &ws;
+        hipStream_t stream;
+        ~Mark() { if (hipEventRecord(ws.last_use, stream) == hipSuccess) ws.pending = true; else (void)hipGetLastError(); }
+    } mark{ws, stream};
+
+    uint32_t *const count = static_cast<uint32_t *>(ws.index.p);
+    uint32_t *const list = reinterpret_cast<uint32_t *>(static_cast<char *>(ws.index.p) + LIST_AT);
+    if (hipError_t e = ldpc::launch_cascade_compact(success, stage, list, count, nb, stream); e != hipSuccess) return e;
+    if (hipError_t e = hipMemcpyAsync(ws.count_host, count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream); e != hipSuccess) return e;
+    if (hipError_t e = hipStreamSynchronize(stream); e != hipSuccess) return e;
+    const size_t failed = *ws.count_host;
+    if (failed == 0) return hipSuccess;
+    if (failed > nb) return hipErrorUnknown;
+
+    const size_t n = ci.n, out_len = ci.output_len();
+    const size_t chunk = std::min(cascade_chunk_frames(n * sizeof(T)), failed);
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t at_out = up(chunk * n * sizeof(T)), at_iters = at_out + up(chunk * out_len), at_ok = at_iters + up(chunk * sizeof(uint32_t));
+    if (hipError_t e = ws.reserve(ws.data, at_ok + up(chunk)); e != hipSuccess) return e;
+    char *const base = static_cast<char *>(ws.data.p);
+    T *const d_llrs = reinterpret_cast<T *>(base);
+    uint8_t *const d_out = reinterpret_cast<uint8_t *>(base + at_out), *const d_ok = reinterpret_cast<uint8_t *>(base + at_ok);
+    uint32_t *const d_iters = reinterpret_cast<uint32_t *>(base + at_iters);
+    for (size_t c0 = 0; c0 < failed; c0 += chunk) {
+        const size_t nc = std::min(chunk, failed - c0);
+        if (hipError_t e = ldpc::launch_cascade_gather<T>(llrs, n, list + c0, nc, d_llrs, stream); e != hipSuccess) return e;
+        if (hipError_t e = stage2(d_llrs, d_out, d_iters, d_ok, nc, stream); e != hipSuccess) return e;
+        if (hipError_t e = ldpc::launch_cascade_scatter(list + c0, nc, d_out, d_iters, d_ok, out_len, output, iters, success, stage, stream);
+            e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace

@@ -14,7 +14,9 @@ quantise the frames on the device -- labrador_ldpc_hip_awgn_i8's clamp(rint(`--l
 and decode them with the fixed-point layered decoder (labrador_ldpc_decode_ms_layered_fixed_batch_i8 / _i16); f32 is
 the default and leaves everything else as it was.  `--fixed-scale NUM/DEN` / `--fixed-offset INT` (with `--llr i8` / `i16` only) decode
 those frames with normalized / offset check messages in integers (labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8 / _i16,
-DESIGN.md 4.8): DEN is a power of two of at most 256, and the offset is in units of the quantiser.
+DESIGN.md 4.8): DEN is a power of two of at most 256, and the offset is in units of the quantiser.  `--schedule cascade` decodes with the two-stage
+entries (labrador_ldpc_decode_ms_cascade_batch_f32 / _i8 / _i16): the flooding decoder at `--maxiters`, then the layered
+decoder of the LLR type at `--max-sweeps` (default: `--maxiters`) on the frames it failed, with the layered schedule's options.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -39,20 +41,24 @@ def sigma_for(code, snr_db: float, noise: str) -> float:
 def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100, batch: int = 65536,
               max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding",
               scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31,
-              scale_num=None, scale_shift=None, fixed_offset=None):
+              scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
     min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
     fixed-point layered decoder on frames quantised as clamp(rint(llr_scale * y), +-llr_lim) (layered schedule, no float correction).
     `scale_num`, `scale_shift`, `fixed_offset`: the fixed-point decoder's integer correction (decode_ms_layered_fixed_batch's
-    scale_num, scale_shift and offset; quantised LLRs only; None, the default, is plain min-sum)."""
-    if schedule not in ("flooding", "layered"):
+    scale_num, scale_shift and offset; quantised LLRs only; None, the default, is plain min-sum).  `schedule` "cascade"
+    (decode_ms_cascade_batch / decode_ms_cascade_fixed_batch): flooding at `maxiters`, then the layered decoder of `llr` with the
+    layered schedule's options at `max_sweeps` (None: `maxiters`) on the frames flooding failed."""
+    if schedule not in ("flooding", "layered", "cascade"):
         raise ValueError(f"unknown schedule {schedule!r}")
-    if schedule != "layered" and (scale != 1.0 or offset != 0.0):
+    if schedule == "flooding" and (scale != 1.0 or offset != 0.0):
         raise ValueError("scale and offset belong to the layered schedule")
+    if schedule != "cascade" and max_sweeps is not None:
+        raise ValueError("max_sweeps belongs to the cascade")
     if llr not in ("f32", "i8", "i16"):
         raise ValueError(f"unknown LLR type {llr!r}")
-    if llr != "f32" and (schedule != "layered" or scale != 1.0 or offset != 0.0):
+    if llr != "f32" and (schedule == "flooding" or scale != 1.0 or offset != 0.0):
         raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
     if llr == "f32" and not (scale_num is None and scale_shift is None and fixed_offset is None):
         raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
@@ -70,11 +76,14 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         cw = code.encode_batch(data)                                         # perftest/src/main.rs:10-12
         if llr != "f32":                                                     # the same noise, quantised by the i8 channel kernel
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
-            out, _, _ = code.decode_ms_layered_fixed_batch(llrs if llr == "i8" else llrs.to(torch.int16), maxiters,
-                                                           scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset)
+            decode = code.decode_ms_cascade_fixed_batch if schedule == "cascade" else code.decode_ms_layered_fixed_batch
+            out = decode(llrs if llr == "i8" else llrs.to(torch.int16), maxiters, scale_num=scale_num, scale_shift=scale_shift,
+                         offset=fixed_offset, **({"max_sweeps": max_sweeps} if schedule == "cascade" else {}))[0]
         else:
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
-            if schedule == "layered":
+            if schedule == "cascade":
+                out = code.decode_ms_cascade_batch(llrs, maxiters, max_sweeps, scale=scale, offset=offset)[0]
+            elif schedule == "layered":
                 out, _, _ = code.decode_ms_layered_batch(llrs, maxiters, scale=scale, offset=offset)
             else:
                 out, _, _ = code.decode_ms_batch(llrs, maxiters)            # :22
@@ -110,7 +119,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--max-bits", type=float, default=5e7)
     ap.add_argument("--max-errors", type=int, default=5000)
-    ap.add_argument("--schedule", choices=["flooding", "layered"], default="flooding")
+    ap.add_argument("--schedule", choices=["flooding", "layered", "cascade"], default="flooding")
+    ap.add_argument("--max-sweeps", type=int, default=None, help="cap of the second stage (--schedule cascade; default: --maxiters)")
     ap.add_argument("--scale", type=float, default=1.0, help="normalized min-sum factor, 0 < scale <= 1 (--schedule layered)")
     ap.add_argument("--offset", type=float, default=0.0, help="offset min-sum term in LLR units, >= 0 (--schedule layered)")
     ap.add_argument("--llr", choices=["f32", "i8", "i16"], default="f32",
@@ -122,9 +132,11 @@ def main(argv=None):
     ap.add_argument("--fixed-offset", type=int, default=None, metavar="INT",
                     help="fixed-point offset min-sum term in units of the quantiser, >= 0 (--llr i8 / i16)")
     args = ap.parse_args(argv)
-    if args.schedule != "layered" and (args.scale != 1.0 or args.offset != 0.0):
+    if args.schedule == "flooding" and (args.scale != 1.0 or args.offset != 0.0):
         ap.error("--scale and --offset need --schedule layered")
-    if args.llr != "f32" and (args.schedule != "layered" or args.scale != 1.0 or args.offset != 0.0):
+    if args.schedule != "cascade" and args.max_sweeps is not None:
+        ap.error("--max-sweeps needs --schedule cascade")
+    if args.llr != "f32" and (args.schedule == "flooding" or args.scale != 1.0 or args.offset != 0.0):
         ap.error("--llr i8 / i16 needs --schedule layered without --scale and --offset")
     if args.llr == "f32" and (args.fixed_scale is not None or args.fixed_offset is not None):
         ap.error("--fixed-scale and --fixed-offset need --schedule layered --llr i8 / i16")
@@ -137,7 +149,7 @@ def main(argv=None):
                                                   args.max_bits, args.max_errors, schedule=args.schedule,
                                                   scale=args.scale, offset=args.offset, llr=args.llr,
                                                   llr_scale=args.llr_scale, llr_lim=args.llr_lim, scale_num=scale_num,
-                                                  scale_shift=scale_shift, fixed_offset=args.fixed_offset)
+                                                  scale_shift=scale_shift, fixed_offset=args.fixed_offset, max_sweeps=args.max_sweeps)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 

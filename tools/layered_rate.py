@@ -10,6 +10,8 @@ Decoders (default: all):
     fixed_i8, fixed_i16                                   labrador_ldpc_decode_ms_layered_fixed_batch_i8 / _i16
     fixed_i8_16_4_0, fixed_i8_13_4_0, fixed_i8_16_4_1     labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8 at that (scale_num,
                                                           scale_shift, offset), on the i8 frames
+    cascade_f32, cascade_i8, cascade_i8_13_4_0            labrador_ldpc_decode_ms_cascade_batch_f32 / _i8: flooding, then the
+                                                          layered decoder (plain; i8 at (13, 4, 0)) on the frames it failed, cap 25 each
 The f32 frames are awgn_frames(dtype="f32"); the i8 frames are the i8 channel kernel's quantisation (8 / 31) of the same job seed, and
 the i16 frames are those widened.  Passes: a flooding decode that succeeds at iteration index i made i passes, a layered one at sweep
 index i made i + 1; a failure counts as 25.  Cases: TC512 3 dB, TM2048 1.7 and 2 dB, TM8192 2 dB.  Default 1 048 576
@@ -18,7 +20,9 @@ Per decoder: `mcw_s` (M codewords/s, the best repetition), `mcw_s_reps`, `spread
 difference has to exceed), `mean_passes`, `failures`, `fer`.  Per case: `unit_equals_layered` (corrected (1, 0) makes exactly the sweeps
 of plain layered decoding, so its ratio is the price of the added instructions and kernel arguments alone), `identity_equals_fixed` (the
 same for fixed_i8_16_4_0 against fixed_i8), every decoder's rate `_over_layered_f32`, every layered decoder's over its flooding
-counterpart's, and every corrected fixed decoder's `_over_fixed_i8`."""
+counterpart's, and every corrected fixed decoder's `_over_fixed_i8`.  A cascade decoder also reports `stage2_share`, the share of frames its
+first stage failed, counts a frame's passes as its flooding iterations plus, for those, 25 and its sweeps, and has its rate over its
+flooding counterpart's and over its layered counterpart's (`CASCADE`)."""
 import argparse
 import ctypes
 import json
@@ -39,7 +43,10 @@ FIXED_CORRECTED = {"fixed_i8_16_4_0": (16, 4, 0), "fixed_i8_13_4_0": (13, 4, 0),
 # decoder -> (its frames, its flooding counterpart; None: it is a flooding decoder)
 DECODERS = {"flooding_f32": ("f32", None), "layered_f32": ("f32", "flooding_f32"), **{k: ("f32", "flooding_f32") for k in CORRECTED},
             "flooding_i8": ("i8", None), "fixed_i8": ("i8", "flooding_i8"), "fixed_i16": ("i16", "flooding_i8"),
-            **{k: ("i8", "flooding_i8") for k in FIXED_CORRECTED}}
+            **{k: ("i8", "flooding_i8") for k in FIXED_CORRECTED},
+            "cascade_f32": ("f32", "flooding_f32"), "cascade_i8": ("i8", "flooding_i8"), "cascade_i8_13_4_0": ("i8", "flooding_i8")}
+# cascade decoder -> (its layered counterpart, the fixed-point correction of its second stage)
+CASCADE = {"cascade_f32": ("layered_f32", None), "cascade_i8": ("fixed_i8", None), "cascade_i8_13_4_0": ("fixed_i8_13_4_0", (13, 4, 0))}
 
 
 def corrected_call(code, llrs, out, it, ok, scale, offset):
@@ -83,6 +90,7 @@ def main():
         out = {k: torch.empty((frames, code.output_len()), dtype=torch.uint8, device=dev) for k in keys}
         it = {k: torch.empty(frames, dtype=torch.int32, device=dev) for k in keys}
         ok = {k: torch.empty(frames, dtype=torch.uint8, device=dev) for k in keys}
+        stage = {k: torch.empty(frames, dtype=torch.uint8, device=dev) for k in keys if k in CASCADE}
 
         def call(k):
             x = llrs[DECODERS[k][0]]
@@ -92,6 +100,12 @@ def main():
                 num, shift, offset = FIXED_CORRECTED[k]
                 return lambda: code.decode_ms_layered_fixed_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], scale_num=num,
                                                                   scale_shift=shift, offset=offset)
+            if k in CASCADE:
+                if k == "cascade_f32":
+                    return lambda: code.decode_ms_cascade_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], stage=stage[k])
+                num, shift, offset = CASCADE[k][1] or (None, None, None)
+                return lambda: code.decode_ms_cascade_fixed_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], stage=stage[k],
+                                                                  scale_num=num, scale_shift=shift, offset=offset)
             method = (code.decode_ms_batch if DECODERS[k][1] is None else
                       code.decode_ms_layered_batch if k == "layered_f32" else code.decode_ms_layered_fixed_batch)
             return lambda: method(x, MAXITERS, output=out[k], iters=it[k], success=ok[k])
@@ -115,19 +129,26 @@ def main():
             case["identity_equals_fixed"] = all(torch.equal(x["fixed_i8"], x["fixed_i8_16_4_0"]) for x in (out, it, ok))
         for key in keys:
             succ = ok[key].to(torch.int64)
-            passes = torch.where(succ == 1, it[key].to(torch.int64) + (0 if DECODERS[key][1] is None else 1), torch.full_like(succ, MAXITERS))
+            if key in CASCADE:                          # a frame of stage 2 had MAXITERS flooding iterations before its sweeps
+                second = stage[key].to(torch.int64)
+                passes = torch.where(succ == 1, it[key].to(torch.int64) + second, torch.full_like(succ, MAXITERS)) + MAXITERS * second
+            else:
+                passes = torch.where(succ == 1, it[key].to(torch.int64) + (0 if DECODERS[key][1] is None else 1),
+                                     torch.full_like(succ, MAXITERS))
             rates = [frames / t / 1e3 for t in ms[key]]
             case[key] = {"mcw_s": round(max(rates), 3), "mcw_s_reps": [round(r, 3) for r in rates],
                          "spread": round((max(rates) - min(rates)) / max(rates), 4),
                          "mean_passes": round(float(passes.double().mean()), 3), "failures": int((succ == 0).sum()),
                          "fer": float(1.0 - succ.double().mean())}
+            if key in CASCADE:
+                case[key]["stage2_share"] = float(stage[key].double().mean())
         for key in keys:
-            for base in ("layered_f32", DECODERS[key][1], "fixed_i8" if key in FIXED_CORRECTED else None):
+            for base in ("layered_f32", DECODERS[key][1], "fixed_i8" if key in FIXED_CORRECTED else None, CASCADE.get(key, (None,))[0]):
                 if base in keys and base != key:
                     case[f"{key}_over_{base}"] = round(case[key]["mcw_s"] / case[base]["mcw_s"], 4)
         res["cases"].append(case)
         print(json.dumps(case), file=sys.stderr, flush=True)
-        del llrs, out, it, ok, calls
+        del llrs, out, it, ok, stage, calls
         torch.cuda.empty_cache()
     print(json.dumps(res), flush=True)
 
