@@ -552,6 +552,43 @@ int labrador_ldpc_llrs_to_hard_batch_i32(enum labrador_ldpc_code code, const int
 int labrador_ldpc_llrs_to_hard_batch_f32(enum labrador_ldpc_code code, const float   *llrs, uint8_t *output, size_t batch, const struct labrador_ldpc_hip_opts *opts);
 int labrador_ldpc_llrs_to_hard_batch_f64(enum labrador_ldpc_code code, const double  *llrs, uint8_t *output, size_t batch, const struct labrador_ldpc_hip_opts *opts);
 
+/* Quantised LLRs from f32 soft values: how a receiver that holds float LLRs reaches the integer decoders -- the
+ * flooding i8 / i16 kernels, the fixed-point layered entries and the integer cascade.  For an f32 LLR x, `scale` (finite, > 0) and
+ * `lim` (0 <= lim <= 127 for i8, <= 32767 for i16), the library's one rule (the channel's, labrador_ldpc_hip_awgn_i8):
+ *     p = scale * x                     one f32 multiply, nothing fused into it
+ *     q = 0                             if p is NaN: an erasure
+ *       = clamp(rint(p), -lim, lim)     otherwise; rint to nearest, ties to even
+ * +-inf and products beyond the integer range clamp to +-lim; -0.0 gives 0.
+ *   llrs [batch][n]  f32      q [batch][n]  int8_t / int16_t
+ * With host buffers (opts NULL or MEM_HOST) the frames are quantised where they lie by the library's host code, which follows the
+ * rule exactly (the data is there and the loop is cheaper than the crossing); opts->device / devices are ignored.  With MEM_DEVICE
+ * it is a streaming kernel on opts->stream, asynchronous; `llrs` and `q` must be 16-byte aligned (EINVAL, checked before the device
+ * is selected).  Arguments are checked in this order, all before any device work: `code`; `scale` and `lim`; an empty batch is OK
+ * whatever the pointers; a NULL buffer; opts->memory.  Returns a status code. */
+int labrador_ldpc_quantise_llrs_batch_i8 (enum labrador_ldpc_code code, const float *llrs, int8_t  *q, size_t batch, float scale, int lim,
+                                          const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_quantise_llrs_batch_i16(enum labrador_ldpc_code code, const float *llrs, int16_t *q, size_t batch, float scale, int lim,
+                                          const struct labrador_ldpc_hip_opts *opts);
+
+/* The call a receiver makes: decode f32 LLRs through the integer flooding kernels.  Per frame f, exactly,
+ *     labrador_ldpc_decode_ms_batch_<T> on (labrador_ldpc_quantise_llrs_batch_<T> of frame f at (scale, lim))
+ * at cap max_iters and kernel opts->variant (LABRADOR_LDPC_HIP_VARIANT_BITSLICE included, for i8): output, iters and success are
+ * that entry's, bit for bit.  Host f32 rows cross the link as they are and are quantised on the device; with device sets the frames
+ * are sharded as for every batched entry.  The quantised rows live in a workspace of the library's (per calling thread and device,
+ * grow-only), filled and decoded in chunks of what fits 256 MiB of quantised LLRs, at least 8192 frames
+ * (LABRADOR_LDPC_HIP_QUANT_CHUNK=<frames> lowers that, for tests).  Arguments are checked in this order, all before any device
+ * work: `code`; `scale` and `lim`; an empty batch is OK whatever the pointers; a NULL buffer.  With MEM_DEVICE `output` must be
+ * 8-byte and `llrs` 16-byte aligned, and the call is asynchronous on opts->stream; calls of one thread on different streams are
+ * ordered on the workspace by the library.  It must not be called on a stream that is being captured into a graph.  A variant the
+ * integer type has no kernel for is EUNSUPPORTED, as in labrador_ldpc_decode_ms_batch_*.  Hard output only; the layered entries and
+ * the cascade are reached through labrador_ldpc_quantise_llrs_batch_* followed by their own calls.  Returns a status code. */
+int labrador_ldpc_decode_ms_quantised_batch_i8 (enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
+                                                const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_quantised_batch_i16(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
+                                                const struct labrador_ldpc_hip_opts *opts);
+
 /* Synthetic AWGN frames on the device (harness side of the path; what perftest's ms_trial does
  * per frame at perftest/src/main.rs:10-18, batched): frame f takes codeword (f mod pool) of
  * `codewords` ([pool][n/8] bytes, MSB first), maps bit b to 1-2b, adds sigma*N(0,1) from a

@@ -99,6 +99,8 @@ SYMBOLS = {
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
     **{f"labrador_ldpc_hard_to_llrs_batch_{t}": (_int, [_int, _vp, _vp, _sz, _optp]) for t in ("i8", "i16", "i32", "f32", "f64")},
     **{f"labrador_ldpc_llrs_to_hard_batch_{t}": (_int, [_int, _vp, _vp, _sz, _optp]) for t in ("i8", "i16", "i32", "f32", "f64")},
+    **{f"labrador_ldpc_quantise_llrs_batch_{t}": (_int, [_int, _vp, _vp, _sz, _c.c_float, _int, _optp]) for t in ("i8", "i16")},
+    **{f"labrador_ldpc_decode_ms_quantised_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int, _optp]) for t in ("i8", "i16")},
     "labrador_ldpc_hip_awgn_f32": (_int, [_int, _vp, _sz, _vp, _sz, _c.c_float, _c.c_uint64, _optp]),
     "labrador_ldpc_hip_awgn_i8": (_int, [_int, _vp, _sz, _vp, _sz, _c.c_float, _c.c_float, _int,
                                          _c.c_uint64, _optp]),
@@ -511,19 +513,23 @@ class LDPCCode(enum.IntEnum):
                                 types=("i8", "i16"))
 
     def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=(),
-                    app_dtype=None, with_stage=False, stage=None, types=None):
+                    app_dtype=None, with_stage=False, stage=None, types=None, fn_name=None):
         # soft: the call also writes the marginals to `app` [batch, n + p], which comes back first
         # app_dtype: the dtype of `app` as a suffix ("i32"); None = the dtype of `llrs`
         # extra: arguments of the entry point between max_iters and opts
         # with_stage: the call also writes `stage` [batch] u8, which comes back last
         # types: the LLR types (suffixes) this method takes where the prefix has entries for more; None = whatever the prefix has
+        # fn_name: the entry point itself, where the type of `llrs` does not choose it (the caller has checked that type)
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
         if llrs.ndim != 2 or llrs.shape[1] != self.n():
             raise ValueError("llrs must be [batch, n]")
         batch, np_len = llrs.shape[0], self.n() + self.punctured_bits()
         try:
-            fn = getattr(lib, prefix + _suffix(llrs), None) if types is None or _suffix(llrs) in types else None
+            if fn_name is not None:
+                fn = getattr(lib, fn_name)
+            else:
+                fn = getattr(lib, prefix + _suffix(llrs), None) if types is None or _suffix(llrs) in types else None
         except KeyError:
             fn = None
         if fn is None:
@@ -699,6 +705,46 @@ class LDPCCode(enum.IntEnum):
         _check(getattr(lib, "labrador_ldpc_llrs_to_hard_batch_" + _suffix(llrs))(int(self), _ptr(llrs), _ptr(output), batch, ctypes.byref(opts)))
         return output
 
+    # ---- f32 soft values to the integer decoders ----
+    def quantise_llrs_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, out=None, stream: Optional[int] = None):
+        """llrs[batch, n] float32 -> out[batch, n] of `dtype` ("i8", "i16") by the library's one quantisation rule
+        (labrador_ldpc_quantise_llrs_batch_i8 / _i16): clamp(rint(scale * x), -lim, lim) on the f32 product, ties to even, NaN -> 0.
+        `lim` None is the type's maximum (127 / 32767).  numpy = the library's host loop; a torch CUDA float32 tensor = the kernel,
+        asynchronous on `stream` (`llrs` and `out` 16-byte aligned).  The library checks `scale` and `lim` (LdpcHipError)."""
+        np_dtype = _quantised_dtype(dtype)
+        if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
+            raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
+        if llrs.ndim != 2 or llrs.shape[1] != self.n():
+            raise ValueError("llrs must be [batch, n]")
+        if _suffix_or_none(llrs) != "f32":
+            raise ValueError("llrs must be float32")
+        batch = llrs.shape[0]
+        if _is_torch(llrs):
+            if not (llrs.is_cuda and llrs.is_contiguous()):
+                raise ValueError("llrs must be a contiguous float32 CUDA tensor")
+            opts = _device_opts(llrs, stream)
+        else:
+            llrs = np.ascontiguousarray(llrs)
+            opts = HipOpts(DEVICE_CURRENT, MEM_HOST, None, 0, 0, None)
+        out = _result_buffer(out, llrs, (batch, self.n()), dtype, "out", exact=True)
+        lim = int(np.iinfo(np_dtype).max) if lim is None else operator.index(lim)
+        _check(getattr(lib, "labrador_ldpc_quantise_llrs_batch_" + dtype)(int(self), _ptr(llrs), _ptr(out), batch, float(scale), lim,
+                                                                          ctypes.byref(opts)))
+        return out
+
+    def decode_ms_quantised_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, maxiters: int = 50, output=None,
+                                  iters=None, success=None, variant: int = 0, stream: Optional[int] = None, devices=None):
+        """Decode float32 `llrs[batch, n]` through the integer flooding kernels of `dtype` ("i8", "i16") in one call
+        (labrador_ldpc_decode_ms_quantised_batch_i8 / _i16): per frame exactly decode_ms_batch on quantise_llrs_batch(llrs, dtype,
+        scale, lim), at kernel `variant`.  Buffers, `stream` and `devices` as decode_ms_batch; host rows cross the link as float32
+        and are quantised on the device.  Returns (output, iters, success)."""
+        np_dtype = _quantised_dtype(dtype)
+        if (_is_torch(llrs) or isinstance(llrs, np.ndarray)) and _suffix_or_none(llrs) != "f32":
+            raise ValueError("llrs must be float32")
+        lim = int(np.iinfo(np_dtype).max) if lim is None else operator.index(lim)
+        return self._batch_call(None, llrs, maxiters, output, iters, success, variant, stream, devices, extra=(float(scale), lim),
+                                fn_name="labrador_ldpc_decode_ms_quantised_batch_" + dtype)
+
     # ---- synthetic channel (harness) ----
     def awgn_frames(self, codewords, batch: int, sigma: float, seed: int, dtype="f32",
                     scale: float = 8.0, lim: int = 31, out=None, stream: Optional[int] = None, first_frame: int = 0):
@@ -721,6 +767,20 @@ class LDPCCode(enum.IntEnum):
                                                     out.data_ptr(), first_frame, batch, sigma, scale, lim, seed,
                                                     ctypes.byref(opts)))
         return out
+
+
+def _quantised_dtype(dtype) -> np.dtype:
+    """the numpy dtype of a quantiser's `dtype` argument: "i8" or "i16", anything else is KeyError like the neighbours'"""
+    if dtype not in ("i8", "i16"):
+        raise KeyError(dtype)
+    return _NP_DTYPE[dtype]
+
+
+def _suffix_or_none(a):
+    try:
+        return _suffix(a)
+    except KeyError:
+        return None
 
 
 def _as_u8(a: np.ndarray, length: int, msg: str) -> np.ndarray:

@@ -4,24 +4,27 @@
 
 namespace {
 
-// failed frames per stage-2 launch: what fits 256 MiB of gathered LLRs, at least 8192 (every code's 8192 rows fit 256 MiB, so a
-// chunk's bytes and pieces always fit 32 bits).  LABRADOR_LDPC_HIP_CASCADE_CHUNK=<frames> lowers it, for tests.
-size_t cascade_chunk_frames(size_t llr_row_bytes)
+// Frames per launch on a workspace: what fits 256 MiB of LLR rows, at least 8192 (every code's 8192 rows fit 256 MiB, so a chunk's
+// bytes and pieces always fit 32 bits).  The variable `env` names (=<frames>) lowers it, for tests; it is read per call.
+size_t workspace_chunk_frames(size_t llr_row_bytes, const char *env_name)
 {
     size_t c = ((size_t)256 << 20) / llr_row_bytes;
     if (c < 8192) c = 8192;
-    if (const char *env = std::getenv("LABRADOR_LDPC_HIP_CASCADE_CHUNK")) {
+    if (const char *env = std::getenv(env_name)) {
         const long long v = std::atoll(env);
         if (v > 0 && (size_t)v < c) c = (size_t)v;
     }
     return c;
 }
+// failed frames per stage-2 launch of the cascade
+size_t cascade_chunk_frames(size_t llr_row_bytes) { return workspace_chunk_frames(llr_row_bytes, "LABRADOR_LDPC_HIP_CASCADE_CHUNK"); }
 
 // Device memory between the two stages, grow-only, per calling thread and per device like StagingPool: `index` holds the counter
 // and the list of failed frames of a slice, `data` a chunk's gathered LLRs and dense stage-2 results.  Calls of one thread may use
 // different streams: `last_use` is recorded on a call's stream behind its last use of the workspace, and the next call makes its
 // own stream wait for it before it touches the workspace.  The count comes back through a pinned word, read after the call's own
-// synchronisation, so it needs no such care.
+// synchronisation, so it needs no such care.  The fused quantise-and-decode (capi_quantise.hpp) keeps a second one of these for its
+// quantised rows and uses `data` alone.
 struct CascadeWorkspace {
     struct Block { void *p = nullptr; size_t cap = 0; };
     Block index, data;
@@ -71,6 +74,14 @@ struct CascadeWorkspace {
         b.cap = bytes;
         return hipSuccess;
     }
+    // Before a call's first touch of the workspace: its stream waits for the last use of the call before.
+    hipError_t wait_for_last_use(hipStream_t stream) { return pending ? hipStreamWaitEvent(stream, last_use, 0) : hipSuccess; }
+    // Held from there to the way out, whichever it is: whatever was enqueued in between, the next call waits for it.
+    struct Use {
+        CascadeWorkspace &ws;
+        hipStream_t stream;
+        ~Use() { if (hipEventRecord(ws.last_use, stream) == hipSuccess) ws.pending = true; else (void)hipGetLastError(); }
+    };
 };
 thread_local CascadeWorkspace g_cascade;
 
@@ -86,13 +97,8 @@ hipError_t cascade_slice(const ldpc::CodeInfo &ci, const T *llrs, uint8_t *outpu
     if (hipError_t e = ws.ensure(); e != hipSuccess) return e;
     constexpr size_t LIST_AT = 16;                                  // the counter's word, then the list
     if (hipError_t e = ws.reserve(ws.index, LIST_AT + nb * sizeof(uint32_t)); e != hipSuccess) return e;
-    if (ws.pending)
-        if (hipError_t e = hipStreamWaitEvent(stream, ws.last_use, 0); e != hipSuccess) return e;
-    struct Mark {                                                   // whatever was enqueued below, the next call waits for it
-        CascadeWorkspace &ws;
-        hipStream_t stream;
-        ~Mark() { if (hipEventRecord(ws.last_use, stream) == hipSuccess) ws.pending = true; else (void)hipGetLastError(); }
-    } mark{ws, stream};
+    if (hipError_t e = ws.wait_for_last_use(stream); e != hipSuccess) return e;
+    CascadeWorkspace::Use use{ws, stream};
 
     uint32_t *const count = static_cast<uint32_t *>(ws.index.p);
     uint32_t *const list = reinterpret_cast<uint32_t *>(static_cast<char *>(ws.index.p) + LIST_AT);
