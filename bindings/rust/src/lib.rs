@@ -160,6 +160,12 @@ extern "C" {
     pub fn labrador_ldpc_quantise_llrs_batch_i16(code: LDPCCode, llrs: *const f32, q: *mut i16, batch: usize, scale: f32, lim: c_int, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_quantised_batch_i8(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_quantised_batch_i16(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_quantised_batch_i8(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_quantised_batch_i16(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_quantised_soft_batch_i8(code: LDPCCode, llrs: *const f32, app: *mut i32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_quantised_soft_batch_i16(code: LDPCCode, llrs: *const f32, app: *mut i32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_cascade_quantised_batch_i8(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_cascade_quantised_batch_i16(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_hip_awgn_f32(code: LDPCCode, codewords: *const u8, pool: usize, llrs: *mut f32, batch: usize, sigma: f32, seed: u64, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_hip_awgn_i8(code: LDPCCode, codewords: *const u8, pool: usize, llrs: *mut i8, batch: usize, sigma: f32, scale: f32, lim: c_int, seed: u64, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_hip_awgn_f32_at(code: LDPCCode, codewords: *const u8, pool: usize, llrs: *mut f32, first_frame: u64, batch: usize, sigma: f32, seed: u64, opts: *const HipOpts) -> c_int;

@@ -581,13 +581,67 @@ int labrador_ldpc_quantise_llrs_batch_i16(enum labrador_ldpc_code code, const fl
  * 8-byte and `llrs` 16-byte aligned, and the call is asynchronous on opts->stream; calls of one thread on different streams are
  * ordered on the workspace by the library.  It must not be called on a stream that is being captured into a graph.  A variant the
  * integer type has no kernel for is EUNSUPPORTED, as in labrador_ldpc_decode_ms_batch_*.  Hard output only; the layered entries and
- * the cascade are reached through labrador_ldpc_quantise_llrs_batch_* followed by their own calls.  Returns a status code. */
+ * the cascade have f32-input forms of their own below (labrador_ldpc_decode_ms_layered_quantised_*, _cascade_quantised_*).  Returns a
+ * status code. */
 int labrador_ldpc_decode_ms_quantised_batch_i8 (enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
                                                 uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
                                                 const struct labrador_ldpc_hip_opts *opts);
 int labrador_ldpc_decode_ms_quantised_batch_i16(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
                                                 uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
                                                 const struct labrador_ldpc_hip_opts *opts);
+
+/* f32 LLRs through the fixed-point layered decoders.  Per frame f, exactly,
+ *     labrador_ldpc_decode_ms_layered_fixed_corrected_{,soft_}batch_<T> at (scale_num, scale_shift, offset), variant 0,
+ *     on (labrador_ldpc_quantise_llrs_batch_<T> of frame f at (scale, lim))
+ * at cap max_iters: output, iters, success and `app` (int32 [batch][n + p], the soft forms) are that entry's, bit for bit, for every
+ * f32 input -- +-0, +-inf, NaN (an erasure), denormals and ties included.  The quantiser sits in the kernel's loader, which reads
+ * every LLR once as it fills the marginals: there is no quantised copy of the batch, no workspace and no synchronisation, so with
+ * MEM_DEVICE the call is asynchronous on opts->stream like the fixed-point entries themselves.  An identity triple (1 << k, k, 0)
+ * runs the plain kernel form, whose results are the same.  Host f32 rows cross the link as they are; device sets shard the frames as
+ * for every batched entry.
+ * Arguments are checked in this order, all before any device work: `code`; `scale` and `lim`; an empty batch is OK whatever the
+ * pointers; a NULL buffer (`app` included, where the entry has it); the ranges of the triple; opts->variant != 0 is EUNSUPPORTED.
+ * With MEM_DEVICE `output` must be 8-byte and `app` 16-byte aligned; `llrs` need only be aligned to a float (the kernel loads
+ * single elements).  Returns a status code. */
+int labrador_ldpc_decode_ms_layered_quantised_batch_i8 (enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                        uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
+                                                        uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                        const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_quantised_batch_i16(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                        uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
+                                                        uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                        const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_quantised_soft_batch_i8 (enum labrador_ldpc_code code, const float *llrs, int32_t *app, uint8_t *output,
+                                                             uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                             float scale, int lim, uint32_t scale_num, uint32_t scale_shift,
+                                                             uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_quantised_soft_batch_i16(enum labrador_ldpc_code code, const float *llrs, int32_t *app, uint8_t *output,
+                                                             uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                             float scale, int lim, uint32_t scale_num, uint32_t scale_shift,
+                                                             uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+
+/* f32 LLRs through the integer cascade: the call a receiver wants -- f32 in, the fast integer flooding kernels on
+ * every frame, the fixed-point layered decoder on the frames they fail.  Per frame f, exactly,
+ *     labrador_ldpc_decode_ms_cascade_batch_<T> at (max_iters, max_sweeps, scale_num, scale_shift, offset), stage 1 at opts->variant
+ *     (LABRADOR_LDPC_HIP_VARIANT_BITSLICE included, for i8), on (labrador_ldpc_quantise_llrs_batch_<T> of frame f at (scale, lim))
+ * with output, iters, success and stage as that entry's, bit for bit.  The f32 rows are quantised in chunks into the workspace of
+ * labrador_ldpc_decode_ms_quantised_batch_* (LABRADOR_LDPC_HIP_QUANT_CHUNK), every chunk runs the cascade on its quantised rows, and
+ * stage 2 gathers the failed frames from those (1 or 2 bytes per LLR, not 4) through the cascade's own workspace
+ * (LABRADOR_LDPC_HIP_CASCADE_CHUNK); calls of one thread on different streams are ordered on both workspaces by the library.
+ * Arguments are checked in this order, all before any device work: `code`; `scale` and `lim`; an empty batch is OK whatever the
+ * pointers; a NULL buffer, `stage` included; the ranges of the triple.  With MEM_DEVICE `output` must be 8-byte and `llrs` 16-byte
+ * aligned (the streaming quantiser reads 16-byte pieces).  With MEM_DEVICE the call is NOT purely asynchronous: it SYNCHRONISES
+ * opts->stream ONCE PER CHUNK, for the number of frames stage 1 failed, and returns with the last chunk's stage 2 enqueued, so the
+ * results are valid once the stream is synchronised.  It MUST NOT be called on a stream that is being captured into a graph.
+ * Hard output only.  Returns a status code. */
+int labrador_ldpc_decode_ms_cascade_quantised_batch_i8 (enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                        uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters,
+                                                        size_t max_sweeps, float scale, int lim, uint32_t scale_num,
+                                                        uint32_t scale_shift, uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_quantised_batch_i16(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                        uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters,
+                                                        size_t max_sweeps, float scale, int lim, uint32_t scale_num,
+                                                        uint32_t scale_shift, uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
 
 /* Synthetic AWGN frames on the device (harness side of the path; what perftest's ms_trial does
  * per frame at perftest/src/main.rs:10-18, batched): frame f takes codeword (f mod pool) of

@@ -101,6 +101,12 @@ SYMBOLS = {
     **{f"labrador_ldpc_llrs_to_hard_batch_{t}": (_int, [_int, _vp, _vp, _sz, _optp]) for t in ("i8", "i16", "i32", "f32", "f64")},
     **{f"labrador_ldpc_quantise_llrs_batch_{t}": (_int, [_int, _vp, _vp, _sz, _c.c_float, _int, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_quantised_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int, _optp]) for t in ("i8", "i16")},
+    **{f"labrador_ldpc_decode_ms_layered_quantised_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int, _c.c_uint32,
+                                                                       _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    **{f"labrador_ldpc_decode_ms_layered_quantised_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int,
+                                                                            _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    **{f"labrador_ldpc_decode_ms_cascade_quantised_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _int,
+                                                                       _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
     "labrador_ldpc_hip_awgn_f32": (_int, [_int, _vp, _sz, _vp, _sz, _c.c_float, _c.c_uint64, _optp]),
     "labrador_ldpc_hip_awgn_i8": (_int, [_int, _vp, _sz, _vp, _sz, _c.c_float, _c.c_float, _int,
                                          _c.c_uint64, _optp]),
@@ -744,6 +750,55 @@ class LDPCCode(enum.IntEnum):
         lim = int(np.iinfo(np_dtype).max) if lim is None else operator.index(lim)
         return self._batch_call(None, llrs, maxiters, output, iters, success, variant, stream, devices, extra=(float(scale), lim),
                                 fn_name="labrador_ldpc_decode_ms_quantised_batch_" + dtype)
+
+    def _quantised_call(self, name, llrs, dtype, scale, lim, triple, maxiters, output, iters, success, variant, stream, devices,
+                        caps=(), **kw):
+        """the f32-input calls behind the fixed-point layered decoders and the integer cascade: `dtype` chooses the entry; `caps`
+        (the cascade's max_sweeps), the quantiser's pair and the triple (none given: the identity) go behind maxiters"""
+        np_dtype = _quantised_dtype(dtype)
+        if (_is_torch(llrs) or isinstance(llrs, np.ndarray)) and _suffix_or_none(llrs) != "f32":
+            raise ValueError("llrs must be float32")
+        lim = int(np.iinfo(np_dtype).max) if lim is None else operator.index(lim)
+        extra = (*caps, float(scale), lim, *(_fixed_correction(*triple) or (1, 0, 0)))
+        return self._batch_call(None, llrs, maxiters, output, iters, success, variant, stream, devices, extra=extra, fn_name=name + dtype,
+                                **kw)
+
+    def decode_ms_layered_quantised_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, maxiters: int = 50,
+                                          output=None, iters=None, success=None, variant: int = 0, stream: Optional[int] = None,
+                                          devices=None, scale_num: Optional[int] = None, scale_shift: Optional[int] = None,
+                                          offset: Optional[int] = None):
+        """Decode float32 `llrs[batch, n]` through the fixed-point layered decoder of `dtype` ("i8", "i16") in one call
+        (labrador_ldpc_decode_ms_layered_quantised_batch_i8 / _i16): per frame exactly decode_ms_layered_fixed_batch
+        with `scale_num`, `scale_shift` and `offset` on quantise_llrs_batch(llrs, dtype, scale, lim).  The kernel quantises as it
+        loads: no quantised copy of the batch exists, and with device buffers the call is asynchronous on `stream`.  Buffers,
+        `stream` and `devices` as decode_ms_batch; `variant` 0 is the only kernel.  Returns (output, iters, success)."""
+        return self._quantised_call("labrador_ldpc_decode_ms_layered_quantised_batch_", llrs, dtype, scale, lim,
+                                    (scale_num, scale_shift, offset), maxiters, output, iters, success, variant, stream, devices)
+
+    def decode_ms_layered_quantised_soft_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, maxiters: int = 50,
+                                               app=None, output=None, iters=None, success=None, variant: int = 0,
+                                               stream: Optional[int] = None, devices=None, scale_num: Optional[int] = None,
+                                               scale_shift: Optional[int] = None, offset: Optional[int] = None):
+        """decode_ms_layered_quantised_batch with soft output (labrador_ldpc_decode_ms_layered_quantised_soft_batch_i8 / _i16): also
+        the marginals of the returned sweep, int32 in the units of the quantised LLRs.  Returns (app[batch, n + p] int32, output,
+        iters, success), as decode_ms_layered_fixed_soft_batch on the quantised frames."""
+        return self._quantised_call("labrador_ldpc_decode_ms_layered_quantised_soft_batch_", llrs, dtype, scale, lim,
+                                    (scale_num, scale_shift, offset), maxiters, output, iters, success, variant, stream, devices,
+                                    soft=True, app=app, app_dtype="i32")
+
+    def decode_ms_cascade_quantised_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, maxiters: int = 50,
+                                          max_sweeps: Optional[int] = None, output=None, iters=None, success=None, stage=None,
+                                          variant: int = 0, stream: Optional[int] = None, devices=None, scale_num: Optional[int] = None,
+                                          scale_shift: Optional[int] = None, offset: Optional[int] = None):
+        """Decode float32 `llrs[batch, n]` through the integer cascade of `dtype` ("i8", "i16") in one call
+        (labrador_ldpc_decode_ms_cascade_quantised_batch_i8 / _i16): per frame exactly decode_ms_cascade_fixed_batch
+        -- flooding at cap `maxiters` and kernel `variant`, then the fixed-point layered decoder at cap `max_sweeps` (None =
+        `maxiters`) and the triple on the frames it failed -- on quantise_llrs_batch(llrs, dtype, scale, lim).  With device buffers
+        `llrs` must be 16-byte aligned, the call waits on the stream once per chunk of frames, and it must not run on a stream under
+        capture.  Returns (output, iters, success, stage)."""
+        return self._quantised_call("labrador_ldpc_decode_ms_cascade_quantised_batch_", llrs, dtype, scale, lim,
+                                    (scale_num, scale_shift, offset), maxiters, output, iters, success, variant, stream, devices,
+                                    caps=(maxiters if max_sweeps is None else max_sweeps,), stage=stage, with_stage=True)
 
     # ---- synthetic channel (harness) ----
     def awgn_frames(self, codewords, batch: int, sigma: float, seed: int, dtype="f32",

@@ -32,6 +32,7 @@
 #pragma once
 
 #include "decode_ms_layered.hpp"
+#include "llr_quantise.hpp"              // quantise_llr: the rule of the f32-source loader
 
 namespace ldpc {
 
@@ -87,11 +88,15 @@ LDPC_DEV int bit_mask(uint32_t w)
 // and min2 as they go into the registers -- the minima themselves were taken on the uncorrected |v| -- and every message of the check
 // is built from the corrected pair, now (u_new) and on the next visit (u_old); equal minima correct to equal values, so a tie stays
 // harmless.  The three parameters are wave-uniform kernel arguments; without CORRECTED they are not read.
-template <int CODE, class T, bool SOFT, bool CORRECTED = false>
-LDPC_DEV void decode_ms_layered_fixed_body(const T *__restrict__ llrs, int32_t *__restrict__ app, uint8_t *__restrict__ output,
+//
+// SRC: the element type of `llrs` -- T itself, or float: then the loader, the one place that reads an LLR, quantises
+// it to T by quantise_llr (llr_quantise.hpp) with the wave-uniform (scale, flim), and everything behind the loader is the same code
+// on the same values.  With SRC = T the two are not read.
+template <int CODE, class T, bool SOFT, bool CORRECTED = false, class SRC = T>
+LDPC_DEV void decode_ms_layered_fixed_body(const SRC *__restrict__ llrs, int32_t *__restrict__ app, uint8_t *__restrict__ output,
                                            uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out, uint32_t batch,
                                            uint32_t maxiters, uint32_t *claim, char *lds, uint32_t scale_num = 1, uint32_t scale_shift = 0,
-                                           uint32_t offset = 0)
+                                           uint32_t offset = 0, float scale = 0.0f, float flim = 0.0f)
 {
     using GEO = LayeredFixedGeometry<CODE>;
     constexpr Prototype P = GEO::P;
@@ -99,6 +104,7 @@ LDPC_DEV void decode_ms_layered_fixed_body(const T *__restrict__ llrs, int32_t *
                   NP = GEO::NP, OUT_LEN = GEO::OUT_LEN;
     constexpr int TMAX = sizeof(T) == 1 ? 127 : 32767;
     static_assert(std::is_same_v<T, int8_t> || std::is_same_v<T, int16_t>, "i8 or i16 LLRs");
+    static_assert(std::is_same_v<SRC, T> || std::is_same_v<SRC, float>, "LLRs of T, or f32 LLRs quantised to T by the loader");
 
     const int tid = (int)threadIdx.x;
     const int g = tid / NT;                                  // codeword slot of this thread in the workgroup
@@ -115,7 +121,7 @@ LDPC_DEV void decode_ms_layered_fixed_body(const T *__restrict__ llrs, int32_t *
     while (grp < n_groups) {
         const uint32_t frame = grp * G + g;
         const bool live = frame < batch;                     // (a partial last group: slots beyond the batch decode zeros, store nothing)
-        const T *const L = llrs + (size_t)(live ? frame : 0) * N;
+        const SRC *const L = llrs + (size_t)(live ? frame : 0) * N;
         if (dyn && tid == 0) *next_word = (int)(gridDim.x + __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         if (maxiters == 0) {
             // nothing iterates: output zero, iters 0, no success, every marginal zero
@@ -139,9 +145,16 @@ LDPC_DEV void decode_ms_layered_fixed_body(const T *__restrict__ llrs, int32_t *
                     zr[q][r] = (1u << row_degree(P, r)) - 1u;
                 });
             });
+            // A float row's rounds lie further apart than a load's immediate offset reaches, so each round has an offset of its own.
+            // The thread index is made opaque here, as it is once per layer below: the offsets are formed per codeword, next to their
+            // loads, instead of being held in registers (or in scratch) across the whole kernel.
+            int tq = t;
+            if constexpr (std::is_same_v<SRC, float>) asm volatile("" : "+v"(tq));
             for (int x0 = 0; x0 < NP; x0 += NT) {            // (a wave-uniform trip count: NT divides NP and N)
                 int l = 0;
-                if (x0 < N) l = (int)L[x0 + t];              // (a slot beyond the batch reads frame 0 and drops it: no divergent branch)
+                // (a slot beyond the batch reads frame 0 and drops it: no divergent branch)
+                if constexpr (std::is_same_v<SRC, float>) { if (x0 < N) l = (int)quantise_llr<T>(L[x0 + tq], scale, flim); }
+                else { if (x0 < N) l = (int)L[x0 + t]; }
                 l = live ? l : 0;
                 A[x0 + t] = l < -TMAX ? -TMAX : l;           // (only T's minimum changes)
             }

@@ -46,5 +46,12 @@ template <class T>
 hipError_t launch_decode_ms_layered_fixed_corrected(int code, int variant, const T *llrs, int32_t *app, uint8_t *output, uint32_t *iters,
                                                     uint8_t *success, size_t batch, uint32_t maxiters, uint32_t scale_num,
                                                     uint32_t scale_shift, uint32_t offset, hipStream_t stream);
+// ... in fixed point from f32 LLRs (decode_ms_fixed_quantised.hip): the loader quantises every LLR to T by the rule of
+// llr_quantise.hpp at (scale, lim); `corrected` chooses the form with the correction step, else the triple is not read
+template <class T>
+hipError_t launch_decode_ms_layered_fixed_quantised(int code, int variant, const float *llrs, int32_t *app, uint8_t *output,
+                                                    uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, float scale,
+                                                    int lim, bool corrected, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                    hipStream_t stream);
 
 }  // namespace ldpc

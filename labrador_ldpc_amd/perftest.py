@@ -16,7 +16,10 @@ the default and leaves everything else as it was.  `--fixed-scale NUM/DEN` / `--
 those frames with normalized / offset check messages in integers (labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8 / _i16,
 DESIGN.md 4.8): DEN is a power of two of at most 256, and the offset is in units of the quantiser.  `--schedule cascade` decodes with the two-stage
 entries (labrador_ldpc_decode_ms_cascade_batch_f32 / _i8 / _i16): the flooding decoder at `--maxiters`, then the layered
-decoder of the LLR type at `--max-sweeps` (default: `--maxiters`) on the frames it failed, with the layered schedule's options.
+decoder of the LLR type at `--max-sweeps` (default: `--maxiters`) on the frames it failed, with the layered schedule's options.  `--from-f32` (with `--llr i8` / `i16`
+and `--schedule layered` / `cascade`) generates the f32 frames of the f32 branch instead and decodes them through the f32-input entries
+(labrador_ldpc_decode_ms_layered_quantised_batch_* / _cascade_quantised_batch_*), which quantise at `--llr-scale` /
+`--llr-lim` themselves; without the flag nothing changes.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -41,7 +44,7 @@ def sigma_for(code, snr_db: float, noise: str) -> float:
 def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100, batch: int = 65536,
               max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding",
               scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31,
-              scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None):
+              scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None, from_f32: bool = False):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
     min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
@@ -49,7 +52,9 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     `scale_num`, `scale_shift`, `fixed_offset`: the fixed-point decoder's integer correction (decode_ms_layered_fixed_batch's
     scale_num, scale_shift and offset; quantised LLRs only; None, the default, is plain min-sum).  `schedule` "cascade"
     (decode_ms_cascade_batch / decode_ms_cascade_fixed_batch): flooding at `maxiters`, then the layered decoder of `llr` with the
-    layered schedule's options at `max_sweeps` (None: `maxiters`) on the frames flooding failed."""
+    layered schedule's options at `max_sweeps` (None: `maxiters`) on the frames flooding failed.  `from_f32` (quantised LLRs,
+    layered or cascade): the frames are the f32 frames of the f32 branch, decoded through decode_ms_layered_quantised_batch /
+    decode_ms_cascade_quantised_batch at (`llr_scale`, `llr_lim`)."""
     if schedule not in ("flooding", "layered", "cascade"):
         raise ValueError(f"unknown schedule {schedule!r}")
     if schedule == "flooding" and (scale != 1.0 or offset != 0.0):
@@ -62,6 +67,8 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
     if llr == "f32" and not (scale_num is None and scale_shift is None and fixed_offset is None):
         raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
+    if from_f32 and (llr == "f32" or schedule == "flooding"):
+        raise ValueError("from_f32 belongs to the quantised LLRs of the layered schedule and the cascade")
     import torch
     dev = torch.device("cuda", device)
     k8 = code.k() // 8
@@ -74,7 +81,12 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     while trials * code.k() <= max_bits and errors <= max_errors:
         data = torch.randint(0, 256, (batch, k8), dtype=torch.uint8, device=dev, generator=g)
         cw = code.encode_batch(data)                                         # perftest/src/main.rs:10-12
-        if llr != "f32":                                                     # the same noise, quantised by the i8 channel kernel
+        if from_f32:                                                         # the f32 branch's frames, quantised by the decoder's loader
+            llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)
+            decode = code.decode_ms_cascade_quantised_batch if schedule == "cascade" else code.decode_ms_layered_quantised_batch
+            out = decode(llrs, llr, llr_scale, llr_lim, maxiters, scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset,
+                         **({"max_sweeps": max_sweeps} if schedule == "cascade" else {}))[0]
+        elif llr != "f32":                                                   # the same noise, quantised by the i8 channel kernel
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
             decode = code.decode_ms_cascade_fixed_batch if schedule == "cascade" else code.decode_ms_layered_fixed_batch
             out = decode(llrs if llr == "i8" else llrs.to(torch.int16), maxiters, scale_num=scale_num, scale_shift=scale_shift,
@@ -131,7 +143,11 @@ def main(argv=None):
                     help="fixed-point normalized min-sum factor, DEN a power of two of at most 256 (--llr i8 / i16)")
     ap.add_argument("--fixed-offset", type=int, default=None, metavar="INT",
                     help="fixed-point offset min-sum term in units of the quantiser, >= 0 (--llr i8 / i16)")
+    ap.add_argument("--from-f32", action="store_true",
+                    help="generate f32 frames and decode them through the f32-input entries (--llr i8 / i16, --schedule layered / cascade)")
     args = ap.parse_args(argv)
+    if args.from_f32 and (args.llr == "f32" or args.schedule == "flooding"):
+        ap.error("--from-f32 needs --llr i8 / i16 and --schedule layered or cascade")
     if args.schedule == "flooding" and (args.scale != 1.0 or args.offset != 0.0):
         ap.error("--scale and --offset need --schedule layered")
     if args.schedule != "cascade" and args.max_sweeps is not None:
@@ -149,7 +165,8 @@ def main(argv=None):
                                                   args.max_bits, args.max_errors, schedule=args.schedule,
                                                   scale=args.scale, offset=args.offset, llr=args.llr,
                                                   llr_scale=args.llr_scale, llr_lim=args.llr_lim, scale_num=scale_num,
-                                                  scale_shift=scale_shift, fixed_offset=args.fixed_offset, max_sweeps=args.max_sweeps)
+                                                  scale_shift=scale_shift, fixed_offset=args.fixed_offset, max_sweeps=args.max_sweeps,
+                                                  from_f32=args.from_f32)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 
