@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import edge_frames
+from kernel_inventory import F32_VARIANTS, F64_TUNED, F64_VARIANTS
 import labrador_ldpc_amd as la
 from labrador_ldpc_amd import LDPCCode
 import oracle
@@ -18,16 +19,6 @@ pytestmark = pytest.mark.gpu
 
 ALL = list(LDPCCode)
 CLAMP_CODES = [LDPCCode.TM8192, LDPCCode.TM2048, LDPCCode.TC512, LDPCCode.TM1536]
-# (code, f32) -> every variant with a soft form: the default, the table's alternatives, the pair kernel, the fixed stride, and the forced
-# one / two NaN passes of the register-lean kernels (decode_ms_tables.hpp, decode_ms_launch.hpp)
-F32_VARIANTS = {LDPCCode.TC128: (0, 256), LDPCCode.TC256: (0, 256), LDPCCode.TC512: (0, 256), LDPCCode.TM1280: (0, 256, 512, 1024),
-                LDPCCode.TM1536: (0, 2, 256), LDPCCode.TM2048: (0, 2, 32, 256), LDPCCode.TM5120: (0, 256, 512, 1024),
-                LDPCCode.TM6144: (0, 2, 256), LDPCCode.TM8192: (0, 2, 4, 256)}
-# f64: the default, the workspace kernel (100) and the register-kernel instantiations with a soft form (not in place)
-F64_VARIANTS = {LDPCCode.TC128: (0, 1, 17, 100), LDPCCode.TC256: (0, 1, 17, 100), LDPCCode.TC512: (0, 1, 17, 100),
-                LDPCCode.TM1280: (0, 1, 17, 100), LDPCCode.TM1536: (0, 1, 17, 100), LDPCCode.TM2048: (0, 1, 17, 100),
-                LDPCCode.TM5120: (0, 17, 18, 100), LDPCCode.TM6144: (0, 2, 17, 18, 100), LDPCCode.TM8192: (0, 100)}
-F64_TUNED = (1, 1, 1, 17, 1, 17, 17, 17, 34)          # decode_ms_tables.hpp
 
 
 @pytest.fixture(scope="module", autouse=True)
