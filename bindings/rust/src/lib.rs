@@ -166,6 +166,22 @@ extern "C" {
     pub fn labrador_ldpc_decode_ms_layered_quantised_soft_batch_i16(code: LDPCCode, llrs: *const f32, app: *mut i32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_cascade_quantised_batch_i8(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_cascade_quantised_batch_i16(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_widen_llrs_batch_f16(code: LDPCCode, llrs: *const u16, out: *mut f32, batch: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_widen_llrs_batch_bf16(code: LDPCCode, llrs: *const u16, out: *mut f32, batch: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_batch_f16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_batch_bf16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_soft_batch_f16(code: LDPCCode, llrs: *const u16, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_soft_batch_bf16(code: LDPCCode, llrs: *const u16, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_batch_f16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_batch_bf16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_soft_batch_f16(code: LDPCCode, llrs: *const u16, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_soft_batch_bf16(code: LDPCCode, llrs: *const u16, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_corrected_batch_f16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_corrected_batch_bf16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_corrected_soft_batch_f16(code: LDPCCode, llrs: *const u16, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_layered_corrected_soft_batch_bf16(code: LDPCCode, llrs: *const u16, app: *mut f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_cascade_batch_f16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_cascade_batch_bf16(code: LDPCCode, llrs: *const u16, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale: f32, offset: f32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_hip_awgn_f32(code: LDPCCode, codewords: *const u8, pool: usize, llrs: *mut f32, batch: usize, sigma: f32, seed: u64, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_hip_awgn_i8(code: LDPCCode, codewords: *const u8, pool: usize, llrs: *mut i8, batch: usize, sigma: f32, scale: f32, lim: c_int, seed: u64, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_hip_awgn_f32_at(code: LDPCCode, codewords: *const u8, pool: usize, llrs: *mut f32, first_frame: u64, batch: usize, sigma: f32, seed: u64, opts: *const HipOpts) -> c_int;

@@ -643,6 +643,96 @@ int labrador_ldpc_decode_ms_cascade_quantised_batch_i16(enum labrador_ldpc_code 
                                                         size_t max_sweeps, float scale, int lim, uint32_t scale_num,
                                                         uint32_t scale_shift, uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
 
+/* Half-precision LLRs to the f32 decoders: what a caller whose soft values exist only as IEEE binary16 (f16) or
+ * bfloat16 (bf16) -- a learned demapper's tensors, frames kept in 2 bytes per LLR -- passes instead of an f32 copy.  Both formats
+ * travel as their raw bits, `const uint16_t *`.  The library's one widening rule, widen(h), an f32:
+ *     f16     the exact value: subnormals become the f32 normals they equal, +-0 stays +-0, +-inf stays +-inf; a NaN becomes the
+ *             QUIET f32 NaN of the same sign (payload bits shifted left by 13, bit 22 set)
+ *     bf16    (uint32_t)h << 16 reinterpreted as f32; nothing else, a signalling NaN stays what it is
+ *   llrs [batch][n]  uint16_t      out [batch][n]  f32
+ * With host buffers (opts NULL or MEM_HOST) the frames are widened where they lie by the library's host code, which follows the rule
+ * exactly; opts->device / devices are ignored.  With MEM_DEVICE it is a streaming kernel on opts->stream, asynchronous; `llrs` and
+ * `out` must be 16-byte aligned (EINVAL, checked before the device is selected).  Arguments are checked in this order, all before
+ * any device work: `code`; an empty batch is OK whatever the pointers; a NULL buffer; opts->memory.  Returns a status code. */
+int labrador_ldpc_widen_llrs_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, float *out, size_t batch,
+                                        const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_widen_llrs_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, float *out, size_t batch,
+                                        const struct labrador_ldpc_hip_opts *opts);
+
+/* The flooding f32 decoders on half-precision rows.  Per frame f, exactly,
+ *     labrador_ldpc_decode_ms_batch_f32 / labrador_ldpc_decode_ms_soft_batch_f32 on (widen of frame f)
+ * at cap max_iters and kernel opts->variant: output, iters, success and `app` (f32 [batch][n + p], the soft forms) are that entry's,
+ * bit for bit, for every input -- +-0, subnormals, +-inf and NaN included.  Host rows cross the link AS HALVES and are widened on the
+ * device; with device sets the frames are sharded as for every batched entry.  The widened rows live in a workspace of the
+ * library's (per calling thread and device, grow-only, the one of labrador_ldpc_decode_ms_quantised_batch_*), filled and decoded in
+ * chunks of what fits 256 MiB of f32 LLRs, at least 8192 frames (LABRADOR_LDPC_HIP_WIDEN_CHUNK=<frames> lowers that, for tests).
+ * Arguments are checked as by the f32 entry, in its order and with its texts, all before any device work: `code`; an empty batch is
+ * OK whatever the pointers; a NULL buffer (`app` included, where the entry has it).  With MEM_DEVICE `output` must be 8-byte, `app`
+ * 16-byte and `llrs` 16-byte aligned (the streaming pass reads 16-byte pieces), and the call is asynchronous on opts->stream; calls
+ * of one thread on different streams are ordered on the workspace by the library.  It must not be called on a stream that is being
+ * captured into a graph.  A variant the f32 decoder has no kernel for is EUNSUPPORTED, as in labrador_ldpc_decode_ms_batch_f32.
+ * Returns a status code. */
+int labrador_ldpc_decode_ms_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
+                                       size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
+                                       size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_soft_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, float *app, uint8_t *output, uint32_t *iters,
+                                            uint8_t *success, size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_soft_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, float *app, uint8_t *output, uint32_t *iters,
+                                            uint8_t *success, size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+
+/* The layered f32 decoders on half-precision rows.  Per frame f, exactly, the f32 entry of the same name on (widen of frame f):
+ * output, iters, success and `app` (f32, the soft forms) are that entry's, bit for bit, with the same ranges of `scale` and
+ * `offset`.  The widening sits in the kernel's loader, which reads every LLR as it fills its LDS copy: there is no widened copy of
+ * the batch, no workspace and no synchronisation, so with MEM_DEVICE the call is asynchronous on opts->stream like the f32 entries
+ * themselves.  The plain entries run the corrected kernel at (1, 0), whose results are the plain kernel's.  Host rows
+ * cross the link as halves; device sets shard the frames as for every batched entry.
+ * Arguments are checked in this order, all before any device work: `code`; for the corrected entries the ranges of `scale` and
+ * `offset`; an empty batch is OK whatever the pointers; a NULL buffer (`app` included, where the entry has it); opts->variant != 0
+ * is EUNSUPPORTED (with the f32 entries' text; those say it only after their device checks).  With MEM_DEVICE `output` must be 8-byte
+ * and `app` 16-byte aligned; `llrs` need only be 2-byte aligned (the kernel loads single elements).  Returns a status code. */
+int labrador_ldpc_decode_ms_layered_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_soft_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, float *app, uint8_t *output,
+                                                    uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                    const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_soft_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, float *app, uint8_t *output,
+                                                    uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                    const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_corrected_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters,
+                                                         uint8_t *success, size_t batch, size_t max_iters, float scale, float offset,
+                                                         const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_corrected_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters,
+                                                         uint8_t *success, size_t batch, size_t max_iters, float scale, float offset,
+                                                         const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_corrected_soft_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, float *app, uint8_t *output,
+                                                              uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters, float scale,
+                                                              float offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_layered_corrected_soft_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, float *app, uint8_t *output,
+                                                              uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters, float scale,
+                                                              float offset, const struct labrador_ldpc_hip_opts *opts);
+
+/* The f32 cascade on half-precision rows.  Per frame f, exactly,
+ *     labrador_ldpc_decode_ms_cascade_batch_f32 at (max_iters, max_sweeps, scale, offset), stage 1 at opts->variant, on (widen of
+ *     frame f)
+ * with output, iters, success and stage as that entry's, bit for bit.  The rows are widened in chunks into the workspace of the
+ * flooding entries above (LABRADOR_LDPC_HIP_WIDEN_CHUNK), every chunk runs the cascade on its f32 rows, and stage 2 gathers the
+ * failed frames from those through the cascade's own workspace (LABRADOR_LDPC_HIP_CASCADE_CHUNK) into the f32 layered kernels; calls
+ * of one thread on different streams are ordered on both workspaces by the library.  Arguments are checked in this order, all before
+ * any device work: `code`; the ranges of `scale` and `offset`; an empty batch is OK whatever the pointers; a NULL buffer, `stage`
+ * included.  With MEM_DEVICE `output` must be 8-byte and `llrs` 16-byte aligned.  With MEM_DEVICE the call is NOT purely
+ * asynchronous: like the f32 cascade it SYNCHRONISES opts->stream for the number of frames stage 1 failed, here ONCE PER CHUNK, and
+ * returns with the last chunk's stage 2 enqueued, so the results are valid once the stream is synchronised.  It MUST NOT be called
+ * on a stream that is being captured into a graph.  Hard output only.  Returns a status code. */
+int labrador_ldpc_decode_ms_cascade_batch_f16 (enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters, size_t max_sweeps, float scale,
+                                               float offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_batch_bf16(enum labrador_ldpc_code code, const uint16_t *llrs, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters, size_t max_sweeps, float scale,
+                                               float offset, const struct labrador_ldpc_hip_opts *opts);
+
 /* Synthetic AWGN frames on the device (harness side of the path; what perftest's ms_trial does
  * per frame at perftest/src/main.rs:10-18, batched): frame f takes codeword (f mod pool) of
  * `codewords` ([pool][n/8] bytes, MSB first), maps bit b to 1-2b, adds sigma*N(0,1) from a

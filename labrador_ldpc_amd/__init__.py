@@ -107,6 +107,18 @@ SYMBOLS = {
                                                                             _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_cascade_quantised_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _int,
                                                                        _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    # f16 / bf16 LLRs, as raw bits, to the f32 decoders
+    **{f"labrador_ldpc_widen_llrs_batch_{t}": (_int, [_int, _vp, _vp, _sz, _optp]) for t in ("f16", "bf16")},
+    **{f"labrador_ldpc_decode_ms_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f16", "bf16")},
+    **{f"labrador_ldpc_decode_ms_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f16", "bf16")},
+    **{f"labrador_ldpc_decode_ms_layered_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f16", "bf16")},
+    **{f"labrador_ldpc_decode_ms_layered_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f16", "bf16")},
+    **{f"labrador_ldpc_decode_ms_layered_corrected_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float, _optp])
+       for t in ("f16", "bf16")},
+    **{f"labrador_ldpc_decode_ms_layered_corrected_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float,
+                                                                            _optp]) for t in ("f16", "bf16")},
+    **{f"labrador_ldpc_decode_ms_cascade_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _c.c_float, _optp])
+       for t in ("f16", "bf16")},
     "labrador_ldpc_hip_awgn_f32": (_int, [_int, _vp, _sz, _vp, _sz, _c.c_float, _c.c_uint64, _optp]),
     "labrador_ldpc_hip_awgn_i8": (_int, [_int, _vp, _sz, _vp, _sz, _c.c_float, _c.c_float, _int,
                                          _c.c_uint64, _optp]),
@@ -191,6 +203,10 @@ _NP_SUFFIX = {np.dtype(np.float32): "f32", np.dtype(np.int8): "i8", np.dtype(np.
               np.dtype(np.int32): "i32", np.dtype(np.float64): "f64"}
 _NP_DTYPE = {v: k for k, v in _NP_SUFFIX.items()}
 _TORCH_DTYPE: dict = {}
+# The half-precision LLR types, a table of their own: only the methods that say so take them (the f32 decoders'
+# batched calls and widen_llrs_batch); everything else keeps refusing them through _NP_SUFFIX.  numpy has no bfloat16, so host bf16
+# buffers are not offered from Python (np.uint16 is not taken for one).
+_NP_HALF_SUFFIX = {np.dtype(np.float16): "f16"}
 
 
 def _torch_dtypes() -> dict:
@@ -225,6 +241,14 @@ def _suffix(a) -> str:
     if _is_torch(a):
         return {v: k for k, v in _torch_dtypes().items()}[a.dtype]
     return _NP_SUFFIX[a.dtype]
+
+
+def _half_suffix(a):
+    """"f16" / "bf16" for a half-precision array or tensor, None for anything else"""
+    if _is_torch(a):
+        import torch
+        return {torch.float16: "f16", torch.bfloat16: "bf16"}.get(a.dtype)
+    return _NP_HALF_SUFFIX.get(a.dtype)
 
 
 def _host_opts(stream, variant: int, devices):
@@ -438,8 +462,14 @@ class LDPCCode(enum.IntEnum):
         back; `devices="all"` or a list of HIP ordinals shards the batch over several GPUs);
         torch CUDA tensors are device-resident buffers: the call only enqueues the
         kernel on the tensor's device, on `stream` (default: torch's current stream).
-        Returns (output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8)."""
-        return self._batch_call("labrador_ldpc_decode_ms_batch_", llrs, maxiters, output, iters, success, variant, stream, devices)
+        Returns (output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8).
+
+        Half-precision LLRs -- a numpy float16 array, a torch float16 or bfloat16 tensor -- are decoded by the float32 kernels
+        (labrador_ldpc_decode_ms_batch_f16 / _bf16): per frame exactly this call on the frame widened to float32.
+        Host rows cross the link as halves; a device tensor must be 16-byte aligned.  The same holds for decode_ms_soft_batch,
+        decode_ms_layered_batch, decode_ms_layered_soft_batch and decode_ms_cascade_batch; their `app` is float32."""
+        return self._batch_call("labrador_ldpc_decode_ms_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
+                                half=True)
 
     def decode_ms_layered_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
                                 variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):
@@ -455,9 +485,9 @@ class LDPCCode(enum.IntEnum):
         plain min-sum and call the plain entry point."""
         if scale == 1.0 and offset == 0.0:
             return self._batch_call("labrador_ldpc_decode_ms_layered_batch_", llrs, maxiters, output, iters, success, variant, stream,
-                                    devices)
+                                    devices, half=True)
         return self._batch_call("labrador_ldpc_decode_ms_layered_corrected_batch_", llrs, maxiters, output, iters, success, variant,
-                                stream, devices, extra=(float(scale), float(offset)))
+                                stream, devices, extra=(float(scale), float(offset)), half=True)
 
     def decode_ms_layered_fixed_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
                                       variant: int = 0, stream: Optional[int] = None, devices=None,
@@ -506,7 +536,7 @@ class LDPCCode(enum.IntEnum):
         Returns (output, iters, success, stage)."""
         return self._batch_call("labrador_ldpc_decode_ms_cascade_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
                                 extra=(maxiters if max_sweeps is None else max_sweeps, float(scale), float(offset)), stage=stage,
-                                with_stage=True, types=("f32",))
+                                with_stage=True, types=("f32",), half=True)
 
     def decode_ms_cascade_fixed_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, output=None, iters=None,
                                       success=None, stage=None, variant: int = 0, stream: Optional[int] = None, devices=None,
@@ -519,20 +549,24 @@ class LDPCCode(enum.IntEnum):
                                 types=("i8", "i16"))
 
     def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=(),
-                    app_dtype=None, with_stage=False, stage=None, types=None, fn_name=None):
+                    app_dtype=None, with_stage=False, stage=None, types=None, fn_name=None, half=False):
         # soft: the call also writes the marginals to `app` [batch, n + p], which comes back first
         # app_dtype: the dtype of `app` as a suffix ("i32"); None = the dtype of `llrs`
         # extra: arguments of the entry point between max_iters and opts
         # with_stage: the call also writes `stage` [batch] u8, which comes back last
         # types: the LLR types (suffixes) this method takes where the prefix has entries for more; None = whatever the prefix has
         # fn_name: the entry point itself, where the type of `llrs` does not choose it (the caller has checked that type)
+        # half: float16 / bfloat16 `llrs` choose the prefix's _f16 / _bf16 entry, whose `app` is float32
         if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
             raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
         if llrs.ndim != 2 or llrs.shape[1] != self.n():
             raise ValueError("llrs must be [batch, n]")
         batch, np_len = llrs.shape[0], self.n() + self.punctured_bits()
+        half_suffix = _half_suffix(llrs) if half else None
         try:
-            if fn_name is not None:
+            if half_suffix is not None:
+                fn, app_dtype = getattr(lib, prefix + half_suffix), "f32"
+            elif fn_name is not None:
                 fn = getattr(lib, fn_name)
             else:
                 fn = getattr(lib, prefix + _suffix(llrs), None) if types is None or _suffix(llrs) in types else None
@@ -574,7 +608,7 @@ class LDPCCode(enum.IntEnum):
         variables last --, output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8); output, iters and success are
         what decode_ms_batch returns."""
         return self._batch_call("labrador_ldpc_decode_ms_soft_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
-                                soft=True, app=app)
+                                soft=True, app=app, half=True)
 
     def decode_ms_layered_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
                                      variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):
@@ -583,9 +617,9 @@ class LDPCCode(enum.IntEnum):
         and `offset` as decode_ms_layered_batch (labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32)."""
         if scale == 1.0 and offset == 0.0:
             return self._batch_call("labrador_ldpc_decode_ms_layered_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
-                                    devices, soft=True, app=app)
+                                    devices, soft=True, app=app, half=True)
         return self._batch_call("labrador_ldpc_decode_ms_layered_corrected_soft_batch_", llrs, maxiters, output, iters, success, variant,
-                                stream, devices, soft=True, app=app, extra=(float(scale), float(offset)))
+                                stream, devices, soft=True, app=app, extra=(float(scale), float(offset)), half=True)
 
     def decode_ms_batch_multi(self, parts, maxiters: int = 50, variant: int = 0):
         """Decode several device-resident batches -- one torch CUDA tensor `llrs[frames_i, n]` per part, each on its own (or the
@@ -736,6 +770,31 @@ class LDPCCode(enum.IntEnum):
         lim = int(np.iinfo(np_dtype).max) if lim is None else operator.index(lim)
         _check(getattr(lib, "labrador_ldpc_quantise_llrs_batch_" + dtype)(int(self), _ptr(llrs), _ptr(out), batch, float(scale), lim,
                                                                           ctypes.byref(opts)))
+        return out
+
+    # ---- f16 / bf16 soft values to the f32 decoders ----
+    def widen_llrs_batch(self, llrs, out=None, stream: Optional[int] = None):
+        """llrs[batch, n] float16 (numpy, torch) or bfloat16 (torch) -> out[batch, n] float32 by the library's one widening rule
+        (labrador_ldpc_widen_llrs_batch_f16 / _bf16): f16 to its exact value, a NaN to the quiet NaN of its sign and payload; bf16 to
+        its bits << 16.  numpy = the library's host loop; a torch CUDA tensor = the kernel, asynchronous on `stream` (`llrs` and
+        `out` 16-byte aligned).  The decoders take halves themselves; this is for a caller that wants the float32 rows."""
+        if not (_is_torch(llrs) or isinstance(llrs, np.ndarray)):
+            raise ValueError("llrs must be a numpy array (host) or a torch CUDA tensor (device)")
+        if llrs.ndim != 2 or llrs.shape[1] != self.n():
+            raise ValueError("llrs must be [batch, n]")
+        suffix = _half_suffix(llrs)
+        if suffix is None:
+            raise ValueError("llrs must be float16 or bfloat16")
+        batch = llrs.shape[0]
+        if _is_torch(llrs):
+            if not (llrs.is_cuda and llrs.is_contiguous()):
+                raise ValueError("llrs must be a contiguous CUDA tensor")
+            opts = _device_opts(llrs, stream)
+        else:
+            llrs = np.ascontiguousarray(llrs)
+            opts = HipOpts(DEVICE_CURRENT, MEM_HOST, None, 0, 0, None)
+        out = _result_buffer(out, llrs, (batch, self.n()), "f32", "out", exact=True)
+        _check(getattr(lib, "labrador_ldpc_widen_llrs_batch_" + suffix)(int(self), _ptr(llrs), _ptr(out), batch, ctypes.byref(opts)))
         return out
 
     def decode_ms_quantised_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, maxiters: int = 50, output=None,

@@ -28,6 +28,7 @@
 
 #include "decode_ms_ops.hpp"         // Ops<float>, exclusive_min; static_for, row_block, pi_dev, LDPC_SYNC
 #include "decode_ms_tables.hpp"      // LDPC_TABLE_F32: the flooding default's indices per thread
+#include "llr_widen.hpp"             // widen_llr: the rule of the half-precision loader
 
 namespace ldpc {
 
@@ -87,8 +88,11 @@ LDPC_DEV void layered_sync()
 // CORRECTED: normalized / offset min-sum -- every message magnitude m becomes max(scale * m - offset, +0.0), a rounded
 // f32 multiply and a rounded f32 subtract (0 < scale <= 1, 0 <= offset <= FLT_MAX, checked by capi.hip: m is finite, so neither an
 // infinity nor a NaN can arise).  `scale` and `offset` are wave-uniform kernel arguments; without CORRECTED they are not read.
-template <int CODE, bool SOFT, bool CORRECTED = false>
-LDPC_DEV void decode_ms_layered_body(const float *__restrict__ llrs, float *__restrict__ app, uint8_t *__restrict__ output,
+// SRC: the element type of `llrs` -- float, or f16_llr / bf16_llr: then the two places that read an LLR, the loader
+// and the soft form's second look at a NaN, widen it by widen_llr (llr_widen.hpp), and everything behind them is the same code on the
+// same values.
+template <int CODE, bool SOFT, bool CORRECTED = false, class SRC = float>
+LDPC_DEV void decode_ms_layered_body(const SRC *__restrict__ llrs, float *__restrict__ app, uint8_t *__restrict__ output,
                                      uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out, uint32_t batch,
                                      uint32_t maxiters, uint32_t *claim, char *lds, float scale = 1.0f, float offset = 0.0f)
 {
@@ -116,7 +120,7 @@ LDPC_DEV void decode_ms_layered_body(const float *__restrict__ llrs, float *__re
     while (grp < n_groups) {
         const uint32_t frame = grp * G + g;
         const bool live = frame < batch;                     // (a partial last group: slots beyond the batch decode zeros, store nothing)
-        const float *const L = llrs + (size_t)(live ? frame : 0) * N;
+        const SRC *const L = llrs + (size_t)(live ? frame : 0) * N;
         if (dyn && tid == 0) *next_word = (int)(gridDim.x + __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         if (maxiters == 0) {
             // decoder.rs:374: nothing iterates -- output zero, iters 0, no success, every marginal zero
@@ -133,7 +137,7 @@ LDPC_DEV void decode_ms_layered_body(const float *__restrict__ llrs, float *__re
                 static_for<0, NB>([&](auto b_) LDPC_INLINE { v[q][decltype(b_)::value] = 0.0f; });
             });
             for (int x = t; x < NB * M; x += NT) U[x] = 0.0f;
-            for (int x = t; x < N; x += NT) LL[x] = live ? O::load(L[x]) : 0.0f;
+            for (int x = t; x < N; x += NT) LL[x] = live ? O::load(widen_llr(L[x])) : 0.0f;
             if (t == 0) { vote[0] = 0; vote[1] = 0; }
             auto llr_at = [&](auto col_, int k) LDPC_INLINE -> float {
                 constexpr int col = decltype(col_)::value;
@@ -258,7 +262,7 @@ LDPC_DEV void decode_ms_layered_body(const float *__restrict__ llrs, float *__re
                                     float s = va[q][c] + 0.0f;                                  // (-0.0 -> +0.0)
                                     // only a NaN or +inf LLR makes a +inf marginal (every u is finite): look at the LLR again there
                                     if constexpr (c < NTX) {
-                                        if (s == __builtin_inff()) { const float raw = L[c * M + k]; if (raw != raw) s = raw; }
+                                        if (s == __builtin_inff()) { const float raw = widen_llr(L[c * M + k]); if (raw != raw) s = raw; }
                                     }
                                     app[(size_t)frame * NP + c * M + k] = s;
                                 }

@@ -53,5 +53,10 @@ hipError_t launch_decode_ms_layered_fixed_quantised(int code, int variant, const
                                                     uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, float scale,
                                                     int lim, bool corrected, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
                                                     hipStream_t stream);
+// ... the f32 layered schedule from f16 / bf16 LLRs (decode_ms_half_layered.hip), H = f16_llr / bf16_llr: the loader widens every
+// LLR by the rule of llr_widen.hpp; always the form with the correction step, (1, 0) for the plain entries
+template <class H>
+hipError_t launch_decode_ms_half_layered(int code, int variant, const H *llrs, float *app, uint8_t *output, uint32_t *iters,
+                                         uint8_t *success, size_t batch, uint32_t maxiters, float scale, float offset, hipStream_t stream);
 
 }  // namespace ldpc

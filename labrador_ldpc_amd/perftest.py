@@ -19,7 +19,10 @@ entries (labrador_ldpc_decode_ms_cascade_batch_f32 / _i8 / _i16):
 decoder of the LLR type at `--max-sweeps` (default: `--maxiters`) on the frames it failed, with the layered schedule's options.  `--from-f32` (with `--llr i8` / `i16`
 and `--schedule layered` / `cascade`) generates the f32 frames of the f32 branch instead and decodes them through the f32-input entries
 (labrador_ldpc_decode_ms_layered_quantised_batch_* / _cascade_quantised_batch_*), which quantise at `--llr-scale` /
-`--llr-lim` themselves; without the flag nothing changes.
+`--llr-lim` themselves; without the flag nothing changes.  `--llr f16` / `--llr bf16` (any schedule, with the f32 branch's options)
+round the f32 frames of the f32 branch to the format on the device and decode them through the half-precision entries
+(labrador_ldpc_decode_ms_batch_f16 / _bf16 and their layered and cascade neighbours): what keeping LLRs in two
+bytes costs in BER.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -33,6 +36,9 @@ import argparse
 import sys
 
 import numpy as np
+
+
+FLOAT_LLRS = ("f32", "f16", "bf16")                                          # the f32 decoders' inputs; the others are quantised
 
 
 def sigma_for(code, snr_db: float, noise: str) -> float:
@@ -54,20 +60,21 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     (decode_ms_cascade_batch / decode_ms_cascade_fixed_batch): flooding at `maxiters`, then the layered decoder of `llr` with the
     layered schedule's options at `max_sweeps` (None: `maxiters`) on the frames flooding failed.  `from_f32` (quantised LLRs,
     layered or cascade): the frames are the f32 frames of the f32 branch, decoded through decode_ms_layered_quantised_batch /
-    decode_ms_cascade_quantised_batch at (`llr_scale`, `llr_lim`)."""
+    decode_ms_cascade_quantised_batch at (`llr_scale`, `llr_lim`).  `llr` "f16" / "bf16": the f32 branch with its frames rounded
+    to the format (to nearest, ties to even) and handed to the same methods as half-precision tensors."""
     if schedule not in ("flooding", "layered", "cascade"):
         raise ValueError(f"unknown schedule {schedule!r}")
     if schedule == "flooding" and (scale != 1.0 or offset != 0.0):
         raise ValueError("scale and offset belong to the layered schedule")
     if schedule != "cascade" and max_sweeps is not None:
         raise ValueError("max_sweeps belongs to the cascade")
-    if llr not in ("f32", "i8", "i16"):
+    if llr not in FLOAT_LLRS + ("i8", "i16"):
         raise ValueError(f"unknown LLR type {llr!r}")
-    if llr != "f32" and (schedule == "flooding" or scale != 1.0 or offset != 0.0):
+    if llr not in FLOAT_LLRS and (schedule == "flooding" or scale != 1.0 or offset != 0.0):
         raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
-    if llr == "f32" and not (scale_num is None and scale_shift is None and fixed_offset is None):
+    if llr in FLOAT_LLRS and not (scale_num is None and scale_shift is None and fixed_offset is None):
         raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
-    if from_f32 and (llr == "f32" or schedule == "flooding"):
+    if from_f32 and (llr in FLOAT_LLRS or schedule == "flooding"):
         raise ValueError("from_f32 belongs to the quantised LLRs of the layered schedule and the cascade")
     import torch
     dev = torch.device("cuda", device)
@@ -86,13 +93,15 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
             decode = code.decode_ms_cascade_quantised_batch if schedule == "cascade" else code.decode_ms_layered_quantised_batch
             out = decode(llrs, llr, llr_scale, llr_lim, maxiters, scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset,
                          **({"max_sweeps": max_sweeps} if schedule == "cascade" else {}))[0]
-        elif llr != "f32":                                                   # the same noise, quantised by the i8 channel kernel
+        elif llr not in FLOAT_LLRS:                                          # the same noise, quantised by the i8 channel kernel
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
             decode = code.decode_ms_cascade_fixed_batch if schedule == "cascade" else code.decode_ms_layered_fixed_batch
             out = decode(llrs if llr == "i8" else llrs.to(torch.int16), maxiters, scale_num=scale_num, scale_shift=scale_shift,
                          offset=fixed_offset, **({"max_sweeps": max_sweeps} if schedule == "cascade" else {}))[0]
         else:
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
+            if llr != "f32":                                                 # the same frames as the format keeps them
+                llrs = llrs.to(torch.float16 if llr == "f16" else torch.bfloat16)
             if schedule == "cascade":
                 out = code.decode_ms_cascade_batch(llrs, maxiters, max_sweeps, scale=scale, offset=offset)[0]
             elif schedule == "layered":
@@ -135,8 +144,9 @@ def main(argv=None):
     ap.add_argument("--max-sweeps", type=int, default=None, help="cap of the second stage (--schedule cascade; default: --maxiters)")
     ap.add_argument("--scale", type=float, default=1.0, help="normalized min-sum factor, 0 < scale <= 1 (--schedule layered)")
     ap.add_argument("--offset", type=float, default=0.0, help="offset min-sum term in LLR units, >= 0 (--schedule layered)")
-    ap.add_argument("--llr", choices=["f32", "i8", "i16"], default="f32",
-                    help="LLR type; i8 / i16: the fixed-point layered decoder on quantised frames (--schedule layered)")
+    ap.add_argument("--llr", choices=["f32", "f16", "bf16", "i8", "i16"], default="f32",
+                    help="LLR type; i8 / i16: the fixed-point layered decoder on quantised frames (--schedule layered); "
+                         "f16 / bf16: the f32 frames rounded to the format, through the half-precision entries")
     ap.add_argument("--llr-scale", type=float, default=8.0, help="quantiser: clamp(rint(scale * y), +-lim) (--llr i8 / i16)")
     ap.add_argument("--llr-lim", type=int, default=31, help="quantiser limit, at most 127 (--llr i8 / i16)")
     ap.add_argument("--fixed-scale", type=fixed_scale, default=None, metavar="NUM/DEN",
@@ -146,15 +156,15 @@ def main(argv=None):
     ap.add_argument("--from-f32", action="store_true",
                     help="generate f32 frames and decode them through the f32-input entries (--llr i8 / i16, --schedule layered / cascade)")
     args = ap.parse_args(argv)
-    if args.from_f32 and (args.llr == "f32" or args.schedule == "flooding"):
+    if args.from_f32 and (args.llr in FLOAT_LLRS or args.schedule == "flooding"):
         ap.error("--from-f32 needs --llr i8 / i16 and --schedule layered or cascade")
     if args.schedule == "flooding" and (args.scale != 1.0 or args.offset != 0.0):
         ap.error("--scale and --offset need --schedule layered")
     if args.schedule != "cascade" and args.max_sweeps is not None:
         ap.error("--max-sweeps needs --schedule cascade")
-    if args.llr != "f32" and (args.schedule == "flooding" or args.scale != 1.0 or args.offset != 0.0):
+    if args.llr not in FLOAT_LLRS and (args.schedule == "flooding" or args.scale != 1.0 or args.offset != 0.0):
         ap.error("--llr i8 / i16 needs --schedule layered without --scale and --offset")
-    if args.llr == "f32" and (args.fixed_scale is not None or args.fixed_offset is not None):
+    if args.llr in FLOAT_LLRS and (args.fixed_scale is not None or args.fixed_offset is not None):
         ap.error("--fixed-scale and --fixed-offset need --schedule layered --llr i8 / i16")
     if args.fixed_offset is not None and args.fixed_offset < 0:
         ap.error("--fixed-offset must be >= 0")
