@@ -490,6 +490,50 @@ int labrador_ldpc_decode_ms_cascade_batch_i16(enum labrador_ldpc_code code, cons
                                               uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
                                               const struct labrador_ldpc_hip_opts *opts);
 
+/* Flooding schedule with normalized / offset min-sum (f32 only): labrador_ldpc_decode_ms_batch_f32 and
+ * labrador_ldpc_decode_ms_soft_batch_f32 -- the reference's decode_ms::<f32>, iteration for iteration -- with one step added.  Where an
+ * iteration forms an edge's check message, its magnitude m (min2 of the check if |v| of the edge equals min1, else min1: the
+ * previous iteration's minima, capped at FLT_MAX; zero in iteration 0) becomes
+ *     t  = scale * m         one IEEE f32 multiply, rounded
+ *     t  = t - offset        one IEEE f32 subtract, rounded (never fused with the multiply)
+ *     m' = t > 0 ? t : +0.0
+ * and the signs are applied to m' as they are to m.  Which of min1 / min2 an edge takes is decided on the uncorrected values;
+ * everything else (self-correction, accumulation order, the NaN and -0.0 rules, the stop rule, iters as the 0-based index of the
+ * converging iteration and max_iters on failure, success, output, app, max_iters = 0) is the flooding contract unchanged.
+ *   scale   0 < scale <= 1, unit-free ("normalized min-sum");
+ *   offset  0 <= offset <= FLT_MAX ("offset min-sum"), in the UNITS OF THE LLRS, as for the layered calls above.  The TM codes'
+ *           punctured variables start at 0, and every message into them is a minimum over their neighbours' first messages: an
+ *           offset above those (0.3 for LLRs of the form +-1 + noise at 1.7 dB on TM2048) zeroes them for good and no frame decodes.
+ * One pair per call.  A NaN, an infinity or a value outside these ranges returns LABRADOR_LDPC_HIP_EINVAL (the message names the
+ * parameter), decided with the other argument checks before any device work -- and before the batch is looked at, so an empty batch
+ * with a bad pair is refused too.  With scale = 1 and offset = 0 the step is the identity and the results equal those of
+ * labrador_ldpc_decode_ms_batch_f32 / labrador_ldpc_decode_ms_soft_batch_f32 bit for bit, app included.  The library chooses no
+ * default: DESIGN.md 4.13 gives measured starting points ((0.8125, 0) and (1, 0.1) on TM2048).
+ * One kernel per code -- the code's default f32 flooding kernel with the step -- so `variant` 0 is the only one: any other value
+ * returns LABRADOR_LDPC_HIP_EUNSUPPORTED with the argument checks, before any device work.  The input is always copied in (host
+ * buffers are never read across the link).  Arguments, memory modes, device sets, `stream` and alignment rules as
+ * labrador_ldpc_decode_ms_batch_f32 / labrador_ldpc_decode_ms_soft_batch_f32 (a device `app` 16-byte aligned, a NULL `app` is
+ * EINVAL).  There is no _multi, single-frame, integer, f64, f16 or bf16 form.  Returns a status code. */
+int labrador_ldpc_decode_ms_corrected_batch_f32(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                uint8_t *success, size_t batch, size_t max_iters, float scale, float offset,
+                                                const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_corrected_soft_batch_f32(enum labrador_ldpc_code code, const float *llrs, float *app, uint8_t *output,
+                                                     uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                     float scale, float offset, const struct labrador_ldpc_hip_opts *opts);
+
+/* The f32 cascade with a corrected stage 1: labrador_ldpc_decode_ms_cascade_batch_f32 whose stage 1 is
+ * labrador_ldpc_decode_ms_corrected_batch_f32 at (flooding_scale, flooding_offset); stage 2 -- the layered decoder at (scale, offset)
+ * on the original LLRs of the frames stage 1 failed -- `stage`, `iters` and everything else are that call's.  Both pairs are
+ * range-checked before the batch is looked at (a bad one is EINVAL even with an empty batch).  With flooding_scale = 1 and
+ * flooding_offset = 0 the call IS labrador_ldpc_decode_ms_cascade_batch_f32, opts->variant included; with any other stage-1 pair
+ * `variant` 0 is the only stage-1 kernel and any other value returns LABRADOR_LDPC_HIP_EUNSUPPORTED before any device work.
+ * Returns a status code. */
+int labrador_ldpc_decode_ms_cascade_corrected_batch_f32(enum labrador_ldpc_code code, const float *llrs, uint8_t *output,
+                                                        uint32_t *iters, uint8_t *success, uint8_t *stage, size_t batch,
+                                                        size_t max_iters, size_t max_sweeps, float flooding_scale,
+                                                        float flooding_offset, float scale, float offset,
+                                                        const struct labrador_ldpc_hip_opts *opts);
+
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --
  * llrs[i], output[i] (8-byte aligned), iters[i], success[i], laid out as in labrador_ldpc_decode_ms_batch_* -- are DEVICE memory

@@ -92,6 +92,11 @@ SYMBOLS = {
     **{f"labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_uint32,
                                                                                  _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
     "labrador_ldpc_decode_ms_cascade_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _c.c_float, _optp]),
+    # the flooding schedule with normalized / offset check messages, and the cascade with it as stage 1
+    "labrador_ldpc_decode_ms_corrected_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float, _optp]),
+    "labrador_ldpc_decode_ms_corrected_soft_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _c.c_float, _optp]),
+    "labrador_ldpc_decode_ms_cascade_corrected_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _c.c_float,
+                                                                   _c.c_float, _c.c_float, _optp]),
     **{f"labrador_ldpc_decode_ms_cascade_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32, _c.c_uint32,
                                                              _c.c_uint32, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
@@ -455,7 +460,7 @@ class LDPCCode(enum.IntEnum):
         return bool(ok), int(iters.value)
 
     def decode_ms_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
-                        variant: int = 0, stream: Optional[int] = None, devices=None):
+                        variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):
         """Decode `llrs[batch, n]`.
 
         numpy arrays are host buffers (the call stages them and returns when results are
@@ -467,9 +472,18 @@ class LDPCCode(enum.IntEnum):
         Half-precision LLRs -- a numpy float16 array, a torch float16 or bfloat16 tensor -- are decoded by the float32 kernels
         (labrador_ldpc_decode_ms_batch_f16 / _bf16): per frame exactly this call on the frame widened to float32.
         Host rows cross the link as halves; a device tensor must be 16-byte aligned.  The same holds for decode_ms_soft_batch,
-        decode_ms_layered_batch, decode_ms_layered_soft_batch and decode_ms_cascade_batch; their `app` is float32."""
-        return self._batch_call("labrador_ldpc_decode_ms_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
-                                half=True)
+        decode_ms_layered_batch, decode_ms_layered_soft_batch and decode_ms_cascade_batch; their `app` is float32.
+
+        `scale`, `offset`: normalized / offset min-sum on this, the flooding schedule (labrador_ldpc_decode_ms_corrected_batch_f32,
+        DESIGN.md 4.13) -- every check message magnitude m becomes max(scale * m - offset, 0).  0 < scale <= 1; offset >= 0 is in the
+        units of the LLRs.  The library checks the ranges (LdpcHipError).  The defaults are plain min-sum and call the plain entry
+        point; any other pair takes float32 LLRs only (another dtype, float16 and bfloat16 included, raises LdpcHipError) and
+        `variant` 0 only."""
+        if scale == 1.0 and offset == 0.0:
+            return self._batch_call("labrador_ldpc_decode_ms_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
+                                    half=True)
+        return self._batch_call("labrador_ldpc_decode_ms_corrected_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices, extra=(float(scale), float(offset)), types=("f32",))
 
     def decode_ms_layered_batch(self, llrs, maxiters: int = 50, output=None, iters=None, success=None,
                                 variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):
@@ -527,16 +541,25 @@ class LDPCCode(enum.IntEnum):
 
     def decode_ms_cascade_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, output=None, iters=None, success=None,
                                 stage=None, variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0,
-                                offset: float = 0.0):
+                                offset: float = 0.0, flooding_scale: float = 1.0, flooding_offset: float = 0.0):
         """Two-stage decoding of f32 LLRs (labrador_ldpc_decode_ms_cascade_batch_f32): decode_ms_batch at cap
         `maxiters` and kernel `variant`, then decode_ms_layered_batch at cap `max_sweeps` (None = `maxiters`) and (`scale`,
         `offset`) on the original LLRs of the frames the first stage failed.  `stage[batch]` u8 says whose results a frame carries
         (0 = flooding, 1 = layered) and `iters` is in that stage's unit.  Buffers, `stream` and `devices` as decode_ms_batch, but
         with device buffers the call waits on the stream once for the first stage before it returns with the second enqueued.
-        Returns (output, iters, success, stage)."""
-        return self._batch_call("labrador_ldpc_decode_ms_cascade_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
-                                extra=(maxiters if max_sweeps is None else max_sweeps, float(scale), float(offset)), stage=stage,
-                                with_stage=True, types=("f32",), half=True)
+        Returns (output, iters, success, stage).
+
+        `flooding_scale`, `flooding_offset`: the first stage as decode_ms_batch at that (`scale`, `offset`) pair
+        (labrador_ldpc_decode_ms_cascade_corrected_batch_f32): float32 LLRs and `variant` 0 only.  The defaults
+        are the plain first stage through the entry point above."""
+        if flooding_scale == 1.0 and flooding_offset == 0.0:
+            return self._batch_call("labrador_ldpc_decode_ms_cascade_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                    devices, extra=(maxiters if max_sweeps is None else max_sweeps, float(scale), float(offset)),
+                                    stage=stage, with_stage=True, types=("f32",), half=True)
+        return self._batch_call("labrador_ldpc_decode_ms_cascade_corrected_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices, extra=(maxiters if max_sweeps is None else max_sweeps, float(flooding_scale),
+                                                float(flooding_offset), float(scale), float(offset)),
+                                stage=stage, with_stage=True, types=("f32",))
 
     def decode_ms_cascade_fixed_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, output=None, iters=None,
                                       success=None, stage=None, variant: int = 0, stream: Optional[int] = None, devices=None,
@@ -600,15 +623,18 @@ class LDPCCode(enum.IntEnum):
         return results
 
     def decode_ms_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
-                             variant: int = 0, stream: Optional[int] = None, devices=None):
+                             variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):
         """decode_ms_batch with soft output: also the decoder's a-posteriori LLR of every variable, the reference's `va`
         (src/decoder.rs:377) when decode_ms returns (labrador_ldpc_decode_ms_soft_batch_*).
 
         Buffers and `devices` / `stream` as in decode_ms_batch.  Returns (app[batch, n + p] in the dtype of `llrs` -- punctured
         variables last --, output[batch, output_len] u8, iters[batch] u32/i32, success[batch] u8); output, iters and success are
-        what decode_ms_batch returns."""
-        return self._batch_call("labrador_ldpc_decode_ms_soft_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
-                                soft=True, app=app, half=True)
+        what decode_ms_batch returns.  `scale` and `offset` as decode_ms_batch (labrador_ldpc_decode_ms_corrected_soft_batch_f32)."""
+        if scale == 1.0 and offset == 0.0:
+            return self._batch_call("labrador_ldpc_decode_ms_soft_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
+                                    soft=True, app=app, half=True)
+        return self._batch_call("labrador_ldpc_decode_ms_corrected_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices, soft=True, app=app, extra=(float(scale), float(offset)), types=("f32",))
 
     def decode_ms_layered_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
                                      variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):

@@ -202,12 +202,17 @@ constexpr bool llr_in_lds() { return (CODE == TC512 || CODE == TC128) && std::is
 // SOFT: the form with soft output -- every codeword's marginals (decoder.rs:377, the `va` decode_ms returns with) are also stored
 // to `app` ([batch][n + p], the LLR type), one unit-stride store per owned variable in the epilogue (DESIGN.md "Soft output").
 // The hard-only kernels are SOFT = false, where all of it compiles away.
-template <int CODE, class T, int IPT, int LEAN, int JW, int FORM, int NANPASS = 0, bool SOFT = false>
+// CORRECTED: normalized / offset min-sum -- every check message's magnitude m becomes max(scale * m - offset, 0),
+// one rounded multiply and one rounded subtract, before the signs go on; the choice among the minima is made on the uncorrected
+// values.  (corr_scale, corr_offset) are wave-uniform, range-checked by the host: 0 < scale <= 1, 0 <= offset <= FLT_MAX, so a
+// corrected magnitude never exceeds the uncorrected one and is never -0.0.  Without CORRECTED the two are not read.
+template <int CODE, class T, int IPT, int LEAN, int JW, int FORM, int NANPASS = 0, bool SOFT = false, bool CORRECTED = false>
 LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                              uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                              uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k, char *lds,
-                             T *__restrict__ app = nullptr)
+                             T *__restrict__ app = nullptr, float corr_scale = 1.0f, float corr_offset = 0.0f)
 {
+    static_assert(!CORRECTED || std::is_same_v<T, float>, "the correction step is built for f32 messages");
     using GEO = Geometry<CODE, T, IPT>;
     using O = Ops<T>;
     using R = typename O::R;
@@ -233,6 +238,7 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
     // and publishes the high word (sign) of each exchanged marginal; no array of marginals.
     constexpr bool INPLACE = LEAN == 2;
     static_assert(!(SOFT && INPLACE), "soft output: the in-place form keeps no marginals of the exchanged columns");
+    static_assert(!(CORRECTED && INPLACE), "the correction step is not built into the in-place check phase");
     constexpr int BLK_BYTES = M * SZ;
     constexpr int FLAG_OFF = INPLACE ? NX * BLK_BYTES + NXC * M * 4 : (NX + NXC) * M * SZ;
     auto hi_off = [](int cs) constexpr { return NX * BLK_BYTES + cs * M * 4; };
@@ -702,6 +708,11 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
                 });
                 const int sgn = xor_reduce<D>(sr), par = (WAVE_VERDICT || WG_VERDICT) ? 0 : xor_reduce<D>(xw);
                 exclusive_min<O, D, true, CAP>(a, e);                                       // :391-395, :430-435
+                if constexpr (CORRECTED)
+                    static_for<0, D>([&](auto J_) LDPC_INLINE {
+                        constexpr int J = decltype(J_)::value;
+                        e[J] = __builtin_fmaxf(__fsub_rn(__fmul_rn(corr_scale, e[J]), corr_offset), 0.0f);
+                    });
                 static_for<0, D>([&](auto J_) LDPC_INLINE {
                     constexpr int J = decltype(J_)::value;
                     constexpr int B = row_block(P, Rw, J);
@@ -739,6 +750,11 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
                 a[J] = v[S][B];
             });
             exclusive_min<O, D, true>(a, e);                                           // :391-395, :430-435
+            if constexpr (CORRECTED)
+                static_for<0, D>([&](auto J_) LDPC_INLINE {
+                    constexpr int J = decltype(J_)::value;
+                    e[J] = __builtin_fmaxf(__fsub_rn(__fmul_rn(corr_scale, e[J]), corr_offset), 0.0f);
+                });
             static_for<0, D>([&](auto J_) LDPC_INLINE {
                 constexpr int J = decltype(J_)::value;
                 constexpr int B = row_block(P, Rw, J);
@@ -1132,11 +1148,11 @@ constexpr int min_waves_per_simd()
     return 1;
 }
 
-template <int CODE, class T, int IPT, int LEAN, int FORM, int NANPASS, bool SOFT = false>
+template <int CODE, class T, int IPT, int LEAN, int FORM, int NANPASS, bool SOFT = false, bool CORRECTED = false>
 __device__ __forceinline__ void decode_ms_kernel_main(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                                                       uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                                                       uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, uint32_t claim_k,
-                                                      T *__restrict__ app = nullptr)
+                                                      T *__restrict__ app = nullptr, float corr_scale = 1.0f, float corr_offset = 0.0f)
 {
     using GEO = Geometry<CODE, T, IPT>;
     constexpr int Q = GEO::M / 4;
@@ -1150,17 +1166,17 @@ __device__ __forceinline__ void decode_ms_kernel_main(const T *__restrict__ llrs
     // arrivals of the whole workgroup, whichever copy a wave runs).
     if constexpr (LDPC_QUARTER_SPECIALISE && GEO::G == 1 && GEO::NT == 2 * Q && Q >= 64) {
         if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) < Q)
-            decode_ms_body<CODE, T, IPT, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
+            decode_ms_body<CODE, T, IPT, LEAN, 0, FORM, NANPASS, SOFT, CORRECTED>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app, corr_scale, corr_offset);
         else
-            decode_ms_body<CODE, T, IPT, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
+            decode_ms_body<CODE, T, IPT, LEAN, 1, FORM, NANPASS, SOFT, CORRECTED>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app, corr_scale, corr_offset);
     } else if constexpr (LDPC_QUARTER_SPECIALISE >= 2 && GEO::G == 1 && GEO::NT == 4 * Q && Q >= 64) {
         const int jw = __builtin_amdgcn_readfirstlane((int)threadIdx.x) / Q;
-        if (jw == 0) decode_ms_body<CODE, T, IPT, LEAN, 0, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
-        else if (jw == 1) decode_ms_body<CODE, T, IPT, LEAN, 1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
-        else if (jw == 2) decode_ms_body<CODE, T, IPT, LEAN, 2, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
-        else decode_ms_body<CODE, T, IPT, LEAN, 3, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
+        if (jw == 0) decode_ms_body<CODE, T, IPT, LEAN, 0, FORM, NANPASS, SOFT, CORRECTED>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app, corr_scale, corr_offset);
+        else if (jw == 1) decode_ms_body<CODE, T, IPT, LEAN, 1, FORM, NANPASS, SOFT, CORRECTED>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app, corr_scale, corr_offset);
+        else if (jw == 2) decode_ms_body<CODE, T, IPT, LEAN, 2, FORM, NANPASS, SOFT, CORRECTED>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app, corr_scale, corr_offset);
+        else decode_ms_body<CODE, T, IPT, LEAN, 3, FORM, NANPASS, SOFT, CORRECTED>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app, corr_scale, corr_offset);
     } else {
-        decode_ms_body<CODE, T, IPT, LEAN, -1, FORM, NANPASS, SOFT>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app);
+        decode_ms_body<CODE, T, IPT, LEAN, -1, FORM, NANPASS, SOFT, CORRECTED>(llrs, output, iters_out, success_out, batch, maxiters, nocap_limit, claim, claim_k, lds, app, corr_scale, corr_offset);
     }
 }
 

@@ -58,12 +58,15 @@ constexpr bool all_exchanged_are_pi(const Prototype &p)
 
 // FORM: the self-correction's form (Ops::self_correct): 0 = compare + select, 2 / 3 = the clamp forms
 // SOFT: the soft-output form (decode_ms_body's SOFT): the two adjacent marginals of a thread go to `app` as one store.
-template <int CODE, class T, int JW, int FORM, bool SOFT = false>
+// CORRECTED: normalized / offset min-sum (decode_ms_body's CORRECTED): m -> max(corr_scale * m - corr_offset, 0) on
+// every check message's magnitude, before the signs go on.
+template <int CODE, class T, int JW, int FORM, bool SOFT = false, bool CORRECTED = false>
 LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restrict__ output,
                                   uint32_t *__restrict__ iters_out, uint8_t *__restrict__ success_out,
                                   uint32_t batch, uint32_t maxiters, float nocap_limit, uint32_t *claim, char *lds,
-                                  T *__restrict__ app = nullptr)
+                                  T *__restrict__ app = nullptr, float corr_scale = 1.0f, float corr_offset = 0.0f)
 {
+    static_assert(!CORRECTED || std::is_same_v<T, float>, "the correction step is built for f32 messages");
     using GEO = PairGeometry<CODE, T>;
     using O = Ops<T>;
     using R = typename O::R;
@@ -308,6 +311,11 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                 });
                 const int sgn = xor_reduce<D>(sr), par = xor_reduce<D>(xw);
                 exclusive_min<O, D, true, CAP>(a, e);                                  // :391-395, :430-435
+                if constexpr (CORRECTED)
+                    static_for<0, D>([&](auto J_) LDPC_INLINE {
+                        constexpr int J = decltype(J_)::value;
+                        e[J] = __builtin_fmaxf(__fsub_rn(__fmul_rn(corr_scale, e[J]), corr_offset), 0.0f);
+                    });
                 static_for<0, D>([&](auto J_) LDPC_INLINE {
                     constexpr int J = decltype(J_)::value;
                     constexpr int B = row_block(P, Rw, J);

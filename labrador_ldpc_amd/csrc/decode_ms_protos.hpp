@@ -26,6 +26,13 @@ bool decode_ms_reads_llrs_once(int code, int variant);
 
 const char *decode_ms_i8_kernel_name(int code, int variant, size_t batch);      // decode_ms_i8.hip
 
+// The flooding schedule on f32 LLRs with normalized / offset check messages (decode_ms_flooding_corrected_f32.hip):
+// the code's default f32 kernel with the correction step; scale and offset are the caller's, already range-checked (capi.hip).
+// app == nullptr launches the hard form.  `variant` 0 only: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).
+hipError_t launch_decode_ms_flooding_corrected(int code, int variant, const float *llrs, float *app, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, size_t batch, uint32_t maxiters, float scale, float offset,
+                                               hipStream_t stream);
+
 // The layered schedule (decode_ms_layered_f32.hip).  app == nullptr launches the hard form.  `variant` 0 is the only kernel of every
 // layered launcher: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).
 hipError_t launch_decode_ms_layered(int code, int variant, const float *llrs, float *app, uint8_t *output, uint32_t *iters,

@@ -22,7 +22,10 @@ and `--schedule layered` / `cascade`) generates the f32 frames of the f32 branch
 `--llr-lim` themselves; without the flag nothing changes.  `--llr f16` / `--llr bf16` (any schedule, with the f32 branch's options)
 round the f32 frames of the f32 branch to the format on the device and decode them through the half-precision entries
 (labrador_ldpc_decode_ms_batch_f16 / _bf16 and their layered and cascade neighbours): what keeping LLRs in two
-bytes costs in BER.
+bytes costs in BER.  `--flooding-scale` / `--flooding-offset` (`--schedule flooding` or `cascade`, `--llr f32` only) give the flooding
+decoder -- the whole decode, or the cascade's first stage -- normalized / offset check messages
+(labrador_ldpc_decode_ms_corrected_batch_f32 / labrador_ldpc_decode_ms_cascade_corrected_batch_f32); the offset is in
+the units of the LLRs, as `--offset`; anywhere else they are a ValueError, and the defaults change nothing.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -50,7 +53,8 @@ def sigma_for(code, snr_db: float, noise: str) -> float:
 def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100, batch: int = 65536,
               max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding",
               scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31,
-              scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None, from_f32: bool = False):
+              scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None, from_f32: bool = False,
+              flooding_scale: float = 1.0, flooding_offset: float = 0.0):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
     min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
@@ -61,7 +65,9 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     layered schedule's options at `max_sweeps` (None: `maxiters`) on the frames flooding failed.  `from_f32` (quantised LLRs,
     layered or cascade): the frames are the f32 frames of the f32 branch, decoded through decode_ms_layered_quantised_batch /
     decode_ms_cascade_quantised_batch at (`llr_scale`, `llr_lim`).  `llr` "f16" / "bf16": the f32 branch with its frames rounded
-    to the format (to nearest, ties to even) and handed to the same methods as half-precision tensors."""
+    to the format (to nearest, ties to even) and handed to the same methods as half-precision tensors.  `flooding_scale`,
+    `flooding_offset`: the FLOODING decoder's normalized / offset min-sum correction (decode_ms_batch's `scale` and `offset`; the
+    flooding schedule and the cascade's first stage, f32 LLRs only; the defaults are plain min-sum)."""
     if schedule not in ("flooding", "layered", "cascade"):
         raise ValueError(f"unknown schedule {schedule!r}")
     if schedule == "flooding" and (scale != 1.0 or offset != 0.0):
@@ -76,6 +82,8 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
     if from_f32 and (llr in FLOAT_LLRS or schedule == "flooding"):
         raise ValueError("from_f32 belongs to the quantised LLRs of the layered schedule and the cascade")
+    if (flooding_scale != 1.0 or flooding_offset != 0.0) and (schedule == "layered" or llr != "f32"):
+        raise ValueError("flooding_scale and flooding_offset belong to the flooding schedule and the cascade on f32 LLRs")
     import torch
     dev = torch.device("cuda", device)
     k8 = code.k() // 8
@@ -103,11 +111,12 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
             if llr != "f32":                                                 # the same frames as the format keeps them
                 llrs = llrs.to(torch.float16 if llr == "f16" else torch.bfloat16)
             if schedule == "cascade":
-                out = code.decode_ms_cascade_batch(llrs, maxiters, max_sweeps, scale=scale, offset=offset)[0]
+                out = code.decode_ms_cascade_batch(llrs, maxiters, max_sweeps, scale=scale, offset=offset, flooding_scale=flooding_scale,
+                                                   flooding_offset=flooding_offset)[0]
             elif schedule == "layered":
                 out, _, _ = code.decode_ms_layered_batch(llrs, maxiters, scale=scale, offset=offset)
             else:
-                out, _, _ = code.decode_ms_batch(llrs, maxiters)            # :22
+                out, _, _ = code.decode_ms_batch(llrs, maxiters, scale=flooding_scale, offset=flooding_offset)      # :22
         diff = out[:, :k8] ^ data                                            # :23-28
         per_frame = popcnt[diff.long()].sum(dim=1)
         errors += int(per_frame.sum())
@@ -144,6 +153,10 @@ def main(argv=None):
     ap.add_argument("--max-sweeps", type=int, default=None, help="cap of the second stage (--schedule cascade; default: --maxiters)")
     ap.add_argument("--scale", type=float, default=1.0, help="normalized min-sum factor, 0 < scale <= 1 (--schedule layered)")
     ap.add_argument("--offset", type=float, default=0.0, help="offset min-sum term in LLR units, >= 0 (--schedule layered)")
+    ap.add_argument("--flooding-scale", type=float, default=1.0,
+                    help="normalized min-sum factor of the flooding decoder, 0 < scale <= 1 (--schedule flooding / cascade, --llr f32)")
+    ap.add_argument("--flooding-offset", type=float, default=0.0,
+                    help="offset min-sum term of the flooding decoder in LLR units, >= 0 (--schedule flooding / cascade, --llr f32)")
     ap.add_argument("--llr", choices=["f32", "f16", "bf16", "i8", "i16"], default="f32",
                     help="LLR type; i8 / i16: the fixed-point layered decoder on quantised frames (--schedule layered); "
                          "f16 / bf16: the f32 frames rounded to the format, through the half-precision entries")
@@ -176,7 +189,8 @@ def main(argv=None):
                                                   scale=args.scale, offset=args.offset, llr=args.llr,
                                                   llr_scale=args.llr_scale, llr_lim=args.llr_lim, scale_num=scale_num,
                                                   scale_shift=scale_shift, fixed_offset=args.fixed_offset, max_sweeps=args.max_sweeps,
-                                                  from_f32=args.from_f32)
+                                                  from_f32=args.from_f32, flooding_scale=args.flooding_scale,
+                                                  flooding_offset=args.flooding_offset)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 

@@ -6,12 +6,16 @@ Decoders (default: all):
     layered_f32                                           labrador_ldpc_decode_ms_layered_batch_f32
     corrected_1_0, corrected_0.8125_0, corrected_1_0.1    labrador_ldpc_decode_ms_layered_corrected_batch_f32 at that (scale, offset): the C
                                                           symbol itself, since the Python keywords route (1, 0) to the plain entry
+    flooding_f32_13_16, flooding_f32_o0.1                 labrador_ldpc_decode_ms_corrected_batch_f32 at (0.8125, 0) / (1, 0.1): the flooding
+                                                          schedule with normalized / offset check messages
     flooding_i8                                           labrador_ldpc_decode_ms_batch_i8
     fixed_i8, fixed_i16                                   labrador_ldpc_decode_ms_layered_fixed_batch_i8 / _i16
     fixed_i8_16_4_0, fixed_i8_13_4_0, fixed_i8_16_4_1     labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8 at that (scale_num,
                                                           scale_shift, offset), on the i8 frames
     cascade_f32, cascade_i8, cascade_i8_13_4_0            labrador_ldpc_decode_ms_cascade_batch_f32 / _i8: flooding, then the
                                                           layered decoder (plain; i8 at (13, 4, 0)) on the frames it failed, cap 25 each
+    cascade_f32_fc                                        labrador_ldpc_decode_ms_cascade_corrected_batch_f32: cascade_f32 with its first
+                                                          stage at (0.8125, 0)
 The f32 frames are awgn_frames(dtype="f32"); the i8 frames are the i8 channel kernel's quantisation (8 / 31) of the same job seed, and
 the i16 frames are those widened.  Passes: a flooding decode that succeeds at iteration index i made i passes, a layered one at sweep
 index i made i + 1; a failure counts as 25.  Cases: TC512 3 dB, TM2048 1.7 and 2 dB, TM8192 2 dB.  Default 1 048 576
@@ -22,7 +26,8 @@ of plain layered decoding, so its ratio is the price of the added instructions a
 same for fixed_i8_16_4_0 against fixed_i8), every decoder's rate `_over_layered_f32`, every layered decoder's over its flooding
 counterpart's, and every corrected fixed decoder's `_over_fixed_i8`.  A cascade decoder also reports `stage2_share`, the share of frames its
 first stage failed, counts a frame's passes as its flooding iterations plus, for those, 25 and its sweeps, and has its rate over its
-flooding counterpart's and over its layered counterpart's (`CASCADE`)."""
+flooding counterpart's and over its layered counterpart's (`CASCADE`).  The corrected flooding decoders have their rate
+`_over_flooding_f32`, the plain kernel of the same run, and cascade_f32_fc also `_over_cascade_f32`."""
 import argparse
 import ctypes
 import json
@@ -40,13 +45,14 @@ MAXITERS = 25
 CASES = (("TC512", 3.0), ("TM2048", 1.7), ("TM2048", 2.0), ("TM8192", 2.0))
 CORRECTED = {"corrected_1_0": (1.0, 0.0), "corrected_0.8125_0": (0.8125, 0.0), "corrected_1_0.1": (1.0, 0.1)}
 FIXED_CORRECTED = {"fixed_i8_16_4_0": (16, 4, 0), "fixed_i8_13_4_0": (13, 4, 0), "fixed_i8_16_4_1": (16, 4, 1)}
+FLOODING_CORRECTED = {"flooding_f32_13_16": (0.8125, 0.0), "flooding_f32_o0.1": (1.0, 0.1)}
 # decoder -> (its frames, its flooding counterpart; None: it is a flooding decoder)
-DECODERS = {"flooding_f32": ("f32", None), "layered_f32": ("f32", "flooding_f32"), **{k: ("f32", "flooding_f32") for k in CORRECTED},
+DECODERS = {"flooding_f32": ("f32", None), **{k: ("f32", None) for k in FLOODING_CORRECTED}, "layered_f32": ("f32", "flooding_f32"), **{k: ("f32", "flooding_f32") for k in CORRECTED},
             "flooding_i8": ("i8", None), "fixed_i8": ("i8", "flooding_i8"), "fixed_i16": ("i16", "flooding_i8"),
             **{k: ("i8", "flooding_i8") for k in FIXED_CORRECTED},
-            "cascade_f32": ("f32", "flooding_f32"), "cascade_i8": ("i8", "flooding_i8"), "cascade_i8_13_4_0": ("i8", "flooding_i8")}
+            "cascade_f32": ("f32", "flooding_f32"), "cascade_f32_fc": ("f32", "flooding_f32"), "cascade_i8": ("i8", "flooding_i8"), "cascade_i8_13_4_0": ("i8", "flooding_i8")}
 # cascade decoder -> (its layered counterpart, the fixed-point correction of its second stage)
-CASCADE = {"cascade_f32": ("layered_f32", None), "cascade_i8": ("fixed_i8", None), "cascade_i8_13_4_0": ("fixed_i8_13_4_0", (13, 4, 0))}
+CASCADE = {"cascade_f32": ("layered_f32", None), "cascade_f32_fc": ("layered_f32", None), "cascade_i8": ("fixed_i8", None), "cascade_i8_13_4_0": ("fixed_i8_13_4_0", (13, 4, 0))}
 
 
 def corrected_call(code, llrs, out, it, ok, scale, offset):
@@ -96,6 +102,9 @@ def main():
             x = llrs[DECODERS[k][0]]
             if k in CORRECTED:
                 return lambda: corrected_call(code, x, out[k], it[k], ok[k], *CORRECTED[k])
+            if k in FLOODING_CORRECTED:
+                scale, offset = FLOODING_CORRECTED[k]
+                return lambda: code.decode_ms_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], scale=scale, offset=offset)
             if k in FIXED_CORRECTED:
                 num, shift, offset = FIXED_CORRECTED[k]
                 return lambda: code.decode_ms_layered_fixed_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], scale_num=num,
@@ -103,6 +112,9 @@ def main():
             if k in CASCADE:
                 if k == "cascade_f32":
                     return lambda: code.decode_ms_cascade_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], stage=stage[k])
+                if k == "cascade_f32_fc":
+                    return lambda: code.decode_ms_cascade_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], stage=stage[k],
+                                                                flooding_scale=0.8125)
                 num, shift, offset = CASCADE[k][1] or (None, None, None)
                 return lambda: code.decode_ms_cascade_fixed_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], stage=stage[k],
                                                                   scale_num=num, scale_shift=shift, offset=offset)
@@ -143,7 +155,8 @@ def main():
             if key in CASCADE:
                 case[key]["stage2_share"] = float(stage[key].double().mean())
         for key in keys:
-            for base in ("layered_f32", DECODERS[key][1], "fixed_i8" if key in FIXED_CORRECTED else None, CASCADE.get(key, (None,))[0]):
+            for base in ("layered_f32", DECODERS[key][1], "fixed_i8" if key in FIXED_CORRECTED else None, CASCADE.get(key, (None,))[0],
+                         "flooding_f32" if key in FLOODING_CORRECTED else None, "cascade_f32" if key == "cascade_f32_fc" else None):
                 if base in keys and base != key:
                     case[f"{key}_over_{base}"] = round(case[key]["mcw_s"] / case[base]["mcw_s"], 4)
         res["cases"].append(case)
