@@ -599,7 +599,10 @@ LDPC_DEV void decode_ms_body(const T *__restrict__ llrs, uint8_t *__restrict__ o
         int par_any = 0;          // bit 31 set if any owned check has odd parity
         // LDS addresses of the exchanged edges are two VALU ops each from `tb`; making `tb`
         // opaque per iteration stops the compiler from hoisting all of them into VGPRs that
-        // then stay live across the whole loop (which costs more in spills than it saves).
+        // then stay live across the whole loop (which costs more in spills than it saves: measured in rounds 1-2 on THIS kernel,
+        // whose TM2048 / TM6144 instantiations run at their register budget.  The pair kernel's hard-output f32 instantiations
+        // do hoist them -- its check phase holds the addresses over its whole length anyway, and the loop lost 37 of 290 VALU
+        // instructions for 2 more spilled registers outside it: decode_ms_pair.hpp, HOIST).
         int tb = t * SZ;
         asm volatile("" : "+v"(tb));
         LDPC_SETPRIO(3);

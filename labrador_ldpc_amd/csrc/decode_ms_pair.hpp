@@ -56,6 +56,18 @@ constexpr bool all_exchanged_are_pi(const Prototype &p)
     return true;
 }
 
+// Which instantiations keep their LDS addresses in registers across the iterations (HOIST in the body) instead of forming them
+// again in every phase: 0 = none of them, 1 = formed once per codeword (begin_codeword), 2 = once per kernel.  Adopted for the
+// hard-output f32 kernels (forms 2 and 3).  The soft, the corrected and the i8 / i16 instantiations keep the per-phase form and
+// their device code: none of them has been measured with the hoist (docs/experiments.md, "Pair kernel: LDS addresses out of the
+// iteration loop").
+template <class T, bool SOFT, bool CORRECTED>
+constexpr int pair_hoist_addresses()
+{
+    if (LDPC_PAIR_HOIST >= 0) return LDPC_PAIR_HOIST;
+    return (std::is_same_v<T, float> && !SOFT && !CORRECTED) ? LDPC_PAIR_HOIST_F32 : 0;
+}
+
 // FORM: the self-correction's form (Ops::self_correct): 0 = compare + select, 2 / 3 = the clamp forms
 // SOFT: the soft-output form (decode_ms_body's SOFT): the two adjacent marginals of a thread go to `app` as one store.
 // CORRECTED: normalized / offset min-sum (decode_ms_body's CORRECTED): m -> max(corr_scale * m - corr_offset, 0) on
@@ -84,6 +96,17 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     // show: 8.32-8.33 -> 8.43-8.45 M codewords/s, 2 spilled registers instead of 3 (profiles/r03_kbench/kb13.txt).
     constexpr bool ODD_B64 = LDPC_PAIR_ODD_B64 >= 0 ? LDPC_PAIR_ODD_B64 != 0 : true;
     constexpr int LOCAL_IN_VAR = LDPC_PAIR_LOCAL_IN_VAR >= 0 ? LDPC_PAIR_LOCAL_IN_VAR : (std::is_same_v<T, float> ? 10 : 8);
+    // HOIST: the nine wired addresses of the exchanged edges and the variable phase's own position depend on the thread and the
+    // quarter body alone.  Formed per phase (the opaque `tq` of the phases below) they are 37 of the 290 full-rate VALU instructions
+    // per wave and iteration of a VALU-bound loop: a shift per phase, an add and a mask per rotation read, and a v_or / v_add of
+    // 0x10000 for every block that lies past the 16-bit offset of a ds instruction (the compiler folds the block offsets it can
+    // see into the instructions and is left with those).  Hoisted, each address is formed once, carries the lds_bias() of its
+    // block and is made opaque, so that the compiler neither re-forms it per phase nor splits the block offset off it again:
+    // every access of the loop reaches its block through the instruction's offset alone, 253-257 VALU instructions per
+    // iteration.  The check phase held these registers over its whole length already (the u stores reuse the read addresses), so
+    // the loop's peak pressure does not move; see forget_llrs() for what the allocator parked in scratch around the loop at first.
+    // Measurements: docs/experiments.md, "Pair kernel: LDS addresses out of the iteration loop".
+    constexpr int HOIST = pair_hoist_addresses<T, SOFT, CORRECTED>();
     constexpr bool PRIO_WAVES = true;            // LDPC_SETPRIO (decode_ms_kernel.hpp)
     (void)PRIO_WAVES;
 
@@ -127,7 +150,64 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
         });
     };
 
+    // HOIST: the workgroup's last codeword fetches no successor, and on that path the raw LLRs would keep their old values -- which
+    // made them live across the iterations next to `llr` (eight registers, the first thing the allocator parks in scratch when the
+    // hoisted addresses take theirs: 4 + 4 dwordx2 spill instructions per codeword and clamp mode).  An empty asm that "writes" them
+    // there ends that live range; no instruction is issued for it.
+    auto forget_llrs = [&]() LDPC_INLINE {
+        static_for<0, IPT>([&](auto S_) LDPC_INLINE {
+            static_for<0, NTX>([&](auto C_) LDPC_INLINE {
+                if constexpr (sizeof(T) == 4) { T &x = lraw[decltype(S_)::value][decltype(C_)::value]; asm volatile("" : "=v"(x)); }
+            });
+        });
+    };
+    (void)forget_llrs;
+    // HOIST: had[S][B] = wire(B, S) as request_marginals() forms it; vb[0] = 8t for the blocks below 64 KB, vb[1] = 8t + 64 KB for
+    // the rest (the variable phase touches every block of the region at the thread's own position)
+    constexpr int VB_HI = 0x10000;
+    int had[IPT][NB], vb[2];
+    (void)had; (void)vb;
+    auto hoist_addresses = [&]() LDPC_INLINE {
+        int tq = t;
+        asm volatile("" : "+v"(tq));
+        const int tb8 = tq * 8;
+        vb[0] = tb8;
+        asm volatile("" : "+v"(vb[0]));
+        if constexpr (FLAG_OFF > VB_HI) {
+            vb[1] = tb8 + VB_HI;
+            asm volatile("" : "+v"(vb[1]));
+        }
+        static_for<0, NB>([&](auto B_) LDPC_INLINE {
+            constexpr int B = decltype(B_)::value;
+            if constexpr (exch_slot(P, B) >= 0) {
+                // both regions of the block within the 16-bit offset of the biased address (the + 4: the odd rotations' first store)
+                constexpr int lo = lds_bias(P, B, BLK_BYTES);
+                static_assert(lds_xu_off(P, exch_slot(P, B), BLK_BYTES) - lo + 4 < 0x10000 && lds_xva_off(P, col_slot(P, P.blk[B].col), BLK_BYTES) - lo + 4 < 0x10000);
+                if constexpr (even_c(B)) {
+                    had[0][B] = wire(B_, IC<0>{}, tb8);
+                } else if constexpr (ODD_B64) {
+                    had[0][B] = wire(B_, IC<-1>{}, tb8);
+                    had[1][B] = wire(B_, IC<1>{}, tb8);
+                    asm volatile("" : "+v"(had[1][B]));
+                } else {
+                    had[0][B] = wire(B_, IC<0>{}, tb8);
+                    had[1][B] = wire(B_, IC<1>{}, tb8);
+                    asm volatile("" : "+v"(had[1][B]));
+                }
+                asm volatile("" : "+v"(had[0][B]));
+            }
+        });
+    };
+    // the thread's own position in the block at byte offset `off` of the region
+    auto own = [&](auto OFF_) LDPC_INLINE -> int {
+        constexpr int off = decltype(OFF_)::value;
+        if constexpr (off < VB_HI) return vb[0] + off;
+        else return vb[1] + (off - VB_HI);
+    };
+    (void)own;
+
     auto begin_codeword = [&]() LDPC_INLINE {
+        if constexpr (HOIST == 1) hoist_addresses();
         int tq = t;
         asm volatile("" : "+v"(tq));             // opaque per phase (no address hoisting), but visibly a multiple of 8 below
         const int tb8 = tq * 8;
@@ -180,8 +260,9 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     auto variable_phase = [&](auto BND_, auto FIRST_) LDPC_INLINE {
         constexpr bool FIRST = decltype(FIRST_)::value != 0;
         int tq = t;
-        asm volatile("" : "+v"(tq));             // opaque per phase (no address hoisting), but visibly a multiple of 8 below
+        if constexpr (HOIST == 0) asm volatile("" : "+v"(tq));   // opaque per phase (no address hoisting), but visibly a multiple of 8 below
         const int tb8 = tq * 8;
+        (void)tb8;
         LDPC_SETPRIO(LDPC_PRIO_VAR);
         static_for<0, NCOLS>([&](auto C_) LDPC_INLINE {
             constexpr int C = decltype(C_)::value;
@@ -194,7 +275,9 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                 if constexpr (P.blk[B].col == C) {
                     constexpr int slot = exch_slot(P, B);
                     if constexpr (slot >= 0) {
-                        const ldpc_f2 up = lds2(lds_xu_off(P, slot, BLK_BYTES) + tb8);
+                        ldpc_f2 up;
+                        if constexpr (HOIST != 0) up = lds2(own(IC<lds_xu_off(P, slot, BLK_BYTES)>{}));
+                        else up = lds2(lds_xu_off(P, slot, BLK_BYTES) + tb8);
                         acc0 = O::add(acc0, O::from_lds(up.x));
                         acc1 = O::add(acc1, O::from_lds(up.y));
                     } else {
@@ -206,7 +289,10 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
             va[0][C] = acc0;
             va[1][C] = acc1;
             constexpr int cs = col_slot(P, C);
-            if constexpr (cs >= 0) lds2(lds_xva_off(P, cs, BLK_BYTES) + tb8) = ldpc_f2{O::store(acc0), O::store(acc1)};
+            if constexpr (cs >= 0) {
+                if constexpr (HOIST != 0) lds2(own(IC<lds_xva_off(P, cs, BLK_BYTES)>{})) = ldpc_f2{O::store(acc0), O::store(acc1)};
+                else lds2(lds_xva_off(P, cs, BLK_BYTES) + tb8) = ldpc_f2{O::store(acc0), O::store(acc1)};
+            }
         });
         // the local-edge part of the check update for the first LDPC_PAIR_LOCAL_IN_VAR indices, while the
         // marginal stores drain (this phase is LDS-bound, the check phase VALU-bound)
@@ -228,8 +314,9 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
         constexpr int BND = (!CAP && NOCAP_POSSIBLE) ? 1 : 0;
         int par_any = 0;
         int tq = t;
-        asm volatile("" : "+v"(tq));             // opaque per phase (no address hoisting), but visibly a multiple of 8 below
+        if constexpr (HOIST == 0) asm volatile("" : "+v"(tq));   // opaque per phase (no address hoisting), but visibly a multiple of 8 below
         const int tb8 = tq * 8;
+        (void)tb8;
         LDPC_SETPRIO(3);
         R xs[IPT][NB];
         int ad[IPT][NB];
@@ -240,8 +327,12 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
             if constexpr (slot >= 0) {
                 constexpr int cs = col_slot(P, P.blk[B].col);
                 constexpr int off = lds_xva_off(P, cs, BLK_BYTES) - lds_bias(P, B, BLK_BYTES);
+                if constexpr (HOIST != 0) {
+                    ad[0][B] = had[0][B];
+                    if constexpr (!even_c(B)) ad[1][B] = had[1][B];
+                }
                 if constexpr (even_c(B)) {
-                    ad[0][B] = wire(B_, IC<0>{}, tb8);
+                    if constexpr (HOIST == 0) ad[0][B] = wire(B_, IC<0>{}, tb8);
                     const ldpc_f2 xp = lds2(off + ad[0][B]);
                     xs[0][B] = O::from_lds(xp.x);
                     xs[1][B] = O::from_lds(xp.y);
@@ -249,14 +340,18 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                     // odd phi: the two marginals are the HIGH half of one aligned pair and the LOW half of the next.
                     // Two ds_read_b64 of those pairs (2 LDS cycles each, conflict-free) instead of two
                     // ds_read_b32 whose 8-byte lane stride is a 2-way bank conflict (4 cycles each).
-                    ad[0][B] = wire(B_, IC<-1>{}, tb8);                 // aligned pair (2t + phi - 1, 2t + phi)
-                    ad[1][B] = wire(B_, IC<1>{}, tb8);                  // aligned pair (2t + phi + 1, 2t + phi + 2), wraps with the quarter
+                    if constexpr (HOIST == 0) {
+                        ad[0][B] = wire(B_, IC<-1>{}, tb8);             // aligned pair (2t + phi - 1, 2t + phi)
+                        ad[1][B] = wire(B_, IC<1>{}, tb8);              // aligned pair (2t + phi + 1, 2t + phi + 2), wraps with the quarter
+                    }
                     const ldpc_f2 lo = lds2(off + ad[0][B]), hi = lds2(off + ad[1][B]);
                     xs[0][B] = O::from_lds(lo.y);
                     xs[1][B] = O::from_lds(hi.x);
                 } else {
-                    ad[0][B] = wire(B_, IC<0>{}, tb8);
-                    ad[1][B] = wire(B_, IC<1>{}, tb8);
+                    if constexpr (HOIST == 0) {
+                        ad[0][B] = wire(B_, IC<0>{}, tb8);
+                        ad[1][B] = wire(B_, IC<1>{}, tb8);
+                    }
                     xs[0][B] = O::from_lds(lds1(off + ad[0][B]));
                     xs[1][B] = O::from_lds(lds1(off + ad[1][B]));
                 }
@@ -335,6 +430,7 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
 
     // ---- persistent loop over codewords ----------------------------------------------------------------
     if (t == 0) cap_flag() = 0;
+    if constexpr (HOIST == 2) hoist_addresses();
     LDPC_SYNC();
     // Where the next codeword's LLR loads are issued: before this one's epilogue (f32: 7.35 -> 7.66 M codewords/s, the
     // epilogue covers part of their latency) or at the top of its own turn (i8 / i16: the early loads' raw bytes are
@@ -401,6 +497,7 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
         // the next codeword's LLR loads, issued before this one's epilogue (fixed cost per codeword 2.55 -> 2.12 us)
         const uint32_t g_next = dyn ? (uint32_t)__builtin_amdgcn_readfirstlane(*next_word) : g + gridDim.x;
         if (FETCH_EARLY && g_next < n_groups) fetch_llrs(g_next);
+        else if constexpr (HOIST != 0 && FETCH_EARLY && sizeof(T) == 4) forget_llrs();
         // hard decisions, MSB first (decoder.rs:455-461 / :467-473): lane l of a wave holds positions
         // 128w + 2l and 128w + 2l + 1, so the two ballots are interleaved bit by bit (scalar unit:
         // s_bitreplicate doubles every bit), then bit-reversed per byte

@@ -11,7 +11,8 @@
     defined(LDPC_PRIO_ROWS_LEAN) || defined(LDPC_PRIO_VAR) || defined(LDPC_TM2048_WAVES) || defined(LDPC_PAIR_LOCAL_IN_VAR) || defined(LDPC_PAIR_NOCAP) || \
     defined(LDPC_PAIR_ODD_B64) || defined(LDPC_PRIO_ROWS_PAIR) || defined(LDPC_SELFCORR_CARRY) || defined(LDPC_WAVE_VERDICT) || defined(LDPC_WG_VERDICT) || \
     defined(LDPC_PEEL_FIRST) || defined(LDPC_PAIR_PEEL_FIRST) || defined(LDPC_PAIR_FETCH_EARLY) || defined(LDPC_PAIR_SELFCORR_CARRY) || \
-    defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH)
+    defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH) || \
+    defined(LDPC_PAIR_HOIST) || defined(LDPC_PAIR_HOIST_F32)
 #error "the LDPC_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/)"
 #endif
 #endif
@@ -119,6 +120,15 @@
 // round 1; f32 7.05 -> 6.90 then, 8.33 -> 8.44 with round 3's check phase), 0 / 1 = force.
 #ifndef LDPC_PAIR_ODD_B64
 #define LDPC_PAIR_ODD_B64 -1
+#endif
+// LDS addresses of the loop (the exchanged edges' wired addresses, the variable phase's own position) kept in registers across the
+// iterations: LDPC_PAIR_HOIST -1 = per instantiation (pair_hoist_addresses(): the hard-output f32 kernels), 0 / 1 / 2 = force for
+// every instantiation (off / formed per codeword / formed per kernel); LDPC_PAIR_HOIST_F32 = the mode of the adopted instantiations.
+#ifndef LDPC_PAIR_HOIST
+#define LDPC_PAIR_HOIST -1
+#endif
+#ifndef LDPC_PAIR_HOIST_F32
+#define LDPC_PAIR_HOIST_F32 2
 #endif
 
 // Wave priority over the six (check row, index) steps of the check phase; 3 before them.  A dozen
