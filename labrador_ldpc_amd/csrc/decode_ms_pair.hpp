@@ -68,6 +68,32 @@ constexpr int pair_hoist_addresses()
     return (std::is_same_v<T, float> && !SOFT && !CORRECTED) ? LDPC_PAIR_HOIST_F32 : 0;
 }
 
+// The k-th exchange slot the variable phase reads (it walks the block columns in order, and a column's blocks in order), as a block
+// number; -1 past the last one.
+constexpr int pair_var_read_block(const Prototype &p, int k)
+{
+    for (int c = 0; c < p.n_cols; ++c)
+        for (int b = 0; b < p.n_blocks; ++b)
+            if (p.blk[b].col == c && exch_slot(p, b) >= 0 && k-- == 0) return b;
+    return -1;
+}
+constexpr int pair_var_read_rank(const Prototype &p, int B)
+{
+    for (int k = 0; k < p.n_blocks; ++k)
+        if (pair_var_read_block(p, k) == B) return k;
+    return -1;
+}
+
+// How many of the variable phase's exchanged-u reads the loop head issues before it has the verdict on the previous pass (EARLY in
+// the body).  Only the instantiations with hoisted addresses can: the reads go out on the hoisted bases.
+template <int HOIST, int NX>
+constexpr int pair_early_u()
+{
+    if (HOIST == 0 || LDPC_PAIR_PEEL_FIRST == 0) return 0;
+    if (LDPC_PAIR_EARLY_U >= 0) return LDPC_PAIR_EARLY_U < NX ? LDPC_PAIR_EARLY_U : NX;
+    return LDPC_PAIR_EARLY_U_F32 < NX ? LDPC_PAIR_EARLY_U_F32 : NX;
+}
+
 // FORM: the self-correction's form (Ops::self_correct): 0 = compare + select, 2 / 3 = the clamp forms
 // SOFT: the soft-output form (decode_ms_body's SOFT): the two adjacent marginals of a thread go to `app` as one store.
 // CORRECTED: normalized / offset min-sum (decode_ms_body's CORRECTED): m -> max(corr_scale * m - corr_offset, 0) on
@@ -107,6 +133,29 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     // the loop's peak pressure does not move; see forget_llrs() for what the allocator parked in scratch around the loop at first.
     // Measurements: docs/experiments.md, "Pair kernel: LDS addresses out of the iteration loop".
     constexpr int HOIST = pair_hoist_addresses<T, SOFT, CORRECTED>();
+    // EARLY: the loop head tested the previous pass's verdict -- one LDS word, a full LDS round trip for every wave of the CU at the same
+    // moment, right behind a barrier and with nothing else resident -- and only then issued the variable phase's u reads: two round trips
+    // in series.  The u reads do not depend on the verdict (nobody writes a u slot before the next check phase, behind another barrier;
+    // on the exit path the epilogue ends with a barrier and the next codeword's peeled pass writes no u slot before its own), so the
+    // first EARLY of them go out right behind the verdict's read and the head waits for the verdict alone (lgkmcnt(EARLY): LDS returns
+    // in order).  The reads are inline asm -- as plain loads the compiler sinks them back below the branch -- so the compiler does not
+    // know that their destinations are pending.  What keeps that safe:
+    //   * continuing path: each pair is first touched by an asm that waits for it ("+v"), in front of its addition, with a count of its
+    //     own (the k-th is back once no more than EARLY - 1 - k operations are outstanding, whatever the compiler issued behind it), so
+    //     that the additions start while the later pairs are still on their way.  Nothing may use, copy or spill a pair between its
+    //     read and that wait;
+    //   * exit path: the pairs are dead there and their registers are reused (fetch_llrs writes VGPRs under vmcnt, which does not order
+    //     against a pending LDS return), so lgkmcnt is drained behind the loop, before the next codeword's LLR loads are issued, and
+    //     nothing on the way there may write one of those registers;
+    //     (both: tests/test_pair_loop_head.py walks every path from the head to the covering wait in the disassembly)
+    //   * a counted wait is sound for LDS alone: no scalar memory load may be outstanding at the head (there is none in the loops);
+    //   * a value out of an asm is divergent to the compiler: the verdict goes through readfirstlane so that the exit stays a scalar
+    //     branch and not an EXEC-masked region (decode_ms_launch.hpp on what those cost TM6144).
+    // Only loads move: va, the marginal stores and the local-edge updates stay behind the verdict (the epilogue needs the previous
+    // pass's va), and the order of the additions is unchanged.  Measurements: docs/experiments.md, "Pair kernel: the u reads ahead of
+    // the verdict".
+    constexpr int EARLY = pair_early_u<HOIST, NX>();
+    static_assert(EARLY >= 0 && EARLY <= 15, "lgkmcnt counts to 15");
     constexpr bool PRIO_WAVES = true;            // LDPC_SETPRIO (decode_ms_kernel.hpp)
     (void)PRIO_WAVES;
 
@@ -136,6 +185,10 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
 
     // ---- state ---------------------------------------------------------------------------------------
     R u[IPT][NB], v[IPT][NB], va[IPT][NCOLS], llr[IPT][NTX];
+    int fnext = 0;                               // EARLY: the byte address of flag_at(it) for the check phase (see `fsel` in iterate)
+    (void)fnext;
+    ldpc_f2 upre[EARLY > 0 ? EARLY : 1];         // EARLY: the u pairs requested at the loop head, in the variable phase's order
+    (void)upre;
     T lraw[IPT][NTX];
 
     auto fetch_llrs = [&](uint32_t c) LDPC_INLINE {
@@ -259,6 +312,8 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     // FIRST_: iteration 0 peeled (LDPC_PAIR_PEEL_FIRST): u == 0 and v == 0, see decode_ms_kernel.hpp PEEL_FIRST
     auto variable_phase = [&](auto BND_, auto FIRST_) LDPC_INLINE {
         constexpr bool FIRST = decltype(FIRST_)::value != 0;
+        constexpr bool PRE = EARLY > 0 && !FIRST;    // the loop head has requested the first EARLY u pairs (request_u_early)
+        (void)PRE;
         int tq = t;
         if constexpr (HOIST == 0) asm volatile("" : "+v"(tq));   // opaque per phase (no address hoisting), but visibly a multiple of 8 below
         const int tb8 = tq * 8;
@@ -276,7 +331,14 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                     constexpr int slot = exch_slot(P, B);
                     if constexpr (slot >= 0) {
                         ldpc_f2 up;
-                        if constexpr (HOIST != 0) up = lds2(own(IC<lds_xu_off(P, slot, BLK_BYTES)>{}));
+                        constexpr int rank = pair_var_read_rank(P, B);
+                        if constexpr (PRE && rank < EARLY) {
+                            // requested at the loop head: wait until no more than the reads behind this one are outstanding
+                            ldpc_f2 &x = upre[rank];
+                            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "n"(EARLY - 1 - rank));
+                            up = x;
+                        }
+                        else if constexpr (HOIST != 0) up = lds2(own(IC<lds_xu_off(P, slot, BLK_BYTES)>{}));
                         else up = lds2(lds_xu_off(P, slot, BLK_BYTES) + tb8);
                         acc0 = O::add(acc0, O::from_lds(up.x));
                         acc1 = O::add(acc1, O::from_lds(up.y));
@@ -425,7 +487,8 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                 par_any |= par;
             });
         });
-        if (par_any < 0) flag_at(it) = 1;
+        if constexpr (EARLY > 0 && !FIRST) { if (par_any < 0) *reinterpret_cast<int *>(lds + fnext) = 1; }     // flag_at(it) = 1
+        else if (par_any < 0) flag_at(it) = 1;
     };
 
     // ---- persistent loop over codewords ----------------------------------------------------------------
@@ -475,6 +538,39 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                 collect_claim();
                 it0 = 1;
             }
+            if constexpr (EARLY > 0) {
+                // (it0 == 1: the peeled build has no `it > 0` to test)
+                // fsel: the byte address of flag_at(it - 1), toggled once per pass and pinned to the scalar unit.  Derived from `it`
+                // and handed to an asm, the address pulls `it`, the cap test and both flag addresses into VGPRs in three of the four
+                // quarter bodies (v_add / v_and / v_xor / v_or with the flags' offset as a literal, per iteration).
+                int fsel = FLAG_OFF;
+                for (uint32_t it = 1;; ++it) {
+                    asm volatile("" : "+s"(it));     // (pinned like fsel: the cap test stays an s_cmp, not a VGPR countdown)
+                    LDPC_SYNC();
+                    int fl, fa;                      // (fa: the address as a VGPR, kept for the store below -- no second v_mov_b32)
+                    asm volatile("" : "+s"(fsel));
+                    asm volatile("v_mov_b32 %0, %2\n\tds_read_b32 %1, %0" : "=&v"(fa), "=v"(fl) : "s"(fsel));          // flag_at(it - 1)
+                    static_for<0, EARLY>([&](auto K_) LDPC_INLINE {
+                        constexpr int K = decltype(K_)::value;
+                        constexpr int off = lds_xu_off(P, exch_slot(P, pair_var_read_block(P, K)), BLK_BYTES);
+                        static_assert((off < VB_HI ? off : off - VB_HI) < 0x10000);
+                        ldpc_f2 &x = upre[K];
+                        const int &base = vb[off < VB_HI ? 0 : 1];          // (an asm operand inside a generic lambda: a named reference)
+                        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(x) : "v"(base), "n"(off < VB_HI ? off : off - VB_HI));
+                    });
+                    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fl) : "n"(EARLY));          // the verdict alone
+                    if (__builtin_amdgcn_readfirstlane(fl) == 0) { done = true; ok = true; iters = it - 1; }   // :453-463
+                    else if (it == maxiters) { done = true; }
+                    if (done) break;                 // (with reads outstanding: drained behind iterate(), see there)
+                    variable_phase(IC<(decltype(CAP_)::value == 0 && NOCAP_POSSIBLE) ? 1 : 0>{}, IC<0>{});
+                    LDPC_SYNC();
+                    if (t == 0) *reinterpret_cast<int *>(lds + fa) = 0;                   // flag_at(it - 1) = 0
+                    fsel ^= 4;
+                    asm volatile("" : "+s"(fsel));
+                    fnext = fsel;
+                    check_phase(it, CAP_, IC<0>{});
+                }
+            } else
             for (uint32_t it = it0;; ++it) {
                 if (it > 0) LDPC_SYNC();          // (the barrier before iteration 0 is taken below, before the clamp mode is read)
                 if (it > 0 && flag_at(it - 1) == 0) { done = true; ok = true; iters = it - 1; }   // :453-463
@@ -493,6 +589,19 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
             else iterate(IC<0>{});
         } else {
             iterate(IC<1>{});
+        }
+        // EARLY: the loop left its head with u reads outstanding, whose destination registers are dead to the compiler and about to be
+        // reused.  (Drained here and not in front of the `break`: an asm in the loop's exit block changes the shape of the loop, 844
+        // spilled VGPRs.)  Nothing between the exit branch and this wait may write one of them.
+        // MAINTENANCE CONSTRAINT: the source cannot enforce that.  Between the loop's exit branch and this wait the compiler schedules
+        // what it likes (today: scalar moves, and in form 2 two v_mov_b32 of constants into other registers) into registers it
+        // believes free, the pending pairs' among them.  The only guard is tests/test_pair_loop_head.py, which walks the
+        // exit path in the disassembly of every loop of forms 2 and 3 and fails when an instruction there names a pending register.
+        // Any statement added between iterate() and this wait, any change to what the loop leaves live, and any compiler upgrade has to
+        // pass that test before it runs; if it cannot, set LDPC_PAIR_EARLY_U_F32 to 0 and leave the asm alone.
+        if constexpr (EARLY > 0) {
+            asm volatile("s_waitcnt lgkmcnt(0)");
+            __builtin_amdgcn_sched_barrier(0);
         }
         // the next codeword's LLR loads, issued before this one's epilogue (fixed cost per codeword 2.55 -> 2.12 us)
         const uint32_t g_next = dyn ? (uint32_t)__builtin_amdgcn_readfirstlane(*next_word) : g + gridDim.x;

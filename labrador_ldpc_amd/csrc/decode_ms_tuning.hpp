@@ -12,7 +12,7 @@
     defined(LDPC_PAIR_ODD_B64) || defined(LDPC_PRIO_ROWS_PAIR) || defined(LDPC_SELFCORR_CARRY) || defined(LDPC_WAVE_VERDICT) || defined(LDPC_WG_VERDICT) || \
     defined(LDPC_PEEL_FIRST) || defined(LDPC_PAIR_PEEL_FIRST) || defined(LDPC_PAIR_FETCH_EARLY) || defined(LDPC_PAIR_SELFCORR_CARRY) || \
     defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH) || \
-    defined(LDPC_PAIR_HOIST) || defined(LDPC_PAIR_HOIST_F32)
+    defined(LDPC_PAIR_HOIST) || defined(LDPC_PAIR_HOIST_F32) || defined(LDPC_PAIR_EARLY_U) || defined(LDPC_PAIR_EARLY_U_F32)
 #error "the LDPC_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/)"
 #endif
 #endif
@@ -129,6 +129,15 @@
 #endif
 #ifndef LDPC_PAIR_HOIST_F32
 #define LDPC_PAIR_HOIST_F32 2
+#endif
+// How many of the variable phase's exchanged-u reads the loop head issues before it has the previous pass's verdict (EARLY in
+// decode_ms_pair_body; only the instantiations with hoisted addresses can): LDPC_PAIR_EARLY_U -1 = per instantiation
+// (LDPC_PAIR_EARLY_U_F32 for the adopted ones), 0 = off, n = the first n the phase consumes (at most all of them).
+#ifndef LDPC_PAIR_EARLY_U
+#define LDPC_PAIR_EARLY_U -1
+#endif
+#ifndef LDPC_PAIR_EARLY_U_F32
+#define LDPC_PAIR_EARLY_U_F32 8
 #endif
 
 // Wave priority over the six (check row, index) steps of the check phase; 3 before them.  A dozen
