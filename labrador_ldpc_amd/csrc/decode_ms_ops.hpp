@@ -444,6 +444,41 @@ LDPC_DEV void exclusive_min(const typename O::R (&a)[D], typename O::R (&e)[D])
     }
 }
 
+// The two halves of exclusive_min() for a caller that finishes some elements later (decode_ms_pair.hpp, DEFER): the partial minimum
+// x[g] "over the other groups" that element J's group is finished with (nothing to keep for D <= 3), and e[J] from it -- the same
+// instruction with the same operand order as exclusive_min() issues for that element, so the value is the same bit for bit.
+template <int D>
+constexpr bool exclusive_min_has_part() { return D >= 4; }
+
+template <class O, int D, bool ABS, bool CAP, int GRP>
+LDPC_DEV typename O::R exclusive_min_part(const typename O::R (&a)[D])
+{
+    static_assert(D >= 4, "rows of degree <= 3 are finished from their elements alone");
+    using R = typename O::R;
+    constexpr int G = (D + 2) / 3;
+    R t[G], x[G];
+    static_for<0, G>([&](auto g_) LDPC_INLINE {
+        constexpr int g = decltype(g_)::value, n = (3 * g + 3 <= D) ? 3 : D - 3 * g;
+        if constexpr (n == 3) t[g] = O::template min3<ABS, ABS, ABS>(a[3 * g], a[3 * g + 1], a[3 * g + 2]);
+        else if constexpr (n == 2) t[g] = O::template min2<ABS, ABS>(a[3 * g], a[3 * g + 1]);
+        else t[g] = ABS ? O::mag(a[3 * g]) : a[3 * g];
+    });
+    exclusive_min<O, G, false, CAP>(t, x);
+    return x[GRP];
+}
+
+template <class O, int D, bool ABS, int J>
+LDPC_DEV typename O::R exclusive_min_finish(const typename O::R (&a)[D], typename O::R xg)
+{
+    static_assert(D >= 3, "rows of degree 1 and 2 have nothing to finish");
+    constexpr int g = J / 3, n = (3 * g + 3 <= D) ? 3 : D - 3 * g;
+    constexpr int o0 = 3 * g + (J % 3 == 0 ? 1 : 0), o1 = 3 * g + (J % 3 == 2 ? 1 : 2);    // the other two of a full group, in order
+    if constexpr (D == 3) return O::template min3_cap<ABS, ABS>(a[o0], a[o1]);
+    else if constexpr (n == 3) return O::template min3<ABS, ABS, false>(a[o0], a[o1], xg);
+    else if constexpr (n == 2) return O::template min2<ABS, false>(a[3 * g + 1 - J % 3], xg);
+    else return xg;
+}
+
 // A marginal as an element of the LLR type: the integer types' registers hold exact integers inside the type's range (IntOps),
 // the others are the type itself.
 template <class T, class R>

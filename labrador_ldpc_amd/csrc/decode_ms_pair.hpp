@@ -94,6 +94,47 @@ constexpr int pair_early_u()
     return LDPC_PAIR_EARLY_U_F32 < NX ? LDPC_PAIR_EARLY_U_F32 : NX;
 }
 
+// Deferred local edges (DEFER in the body).  The order in which a thread's local edges are deferred: by check row, then index, then
+// block -- the edges of one (row, index) share the one sign word that is kept for them, and are taken together.
+constexpr int pair_defer_rank(const Prototype &p, int S, int B)
+{
+    int r = 0;
+    for (int b = 0; b < p.n_blocks; ++b)
+        if (blk_local(p.blk[b])) {
+            if (p.blk[b].row < p.blk[B].row) r += 2;
+            else if (p.blk[b].row == p.blk[B].row) r += (S == 1 ? 1 : 0) + (b < B ? 1 : 0);
+        }
+    return r;
+}
+constexpr bool pair_deferred(const Prototype &p, int S, int B, int defer)
+{
+    return blk_local(p.blk[B]) && pair_defer_rank(p, S, B) < defer;
+}
+// whether the j-th edge of `row` is the first deferred one of its group of three (exclusive_min's groups)
+constexpr bool pair_defer_first_of_group(const Prototype &p, int S, int row, int j, int defer)
+{
+    for (int k = j / 3 * 3; k < j; ++k)
+        if (pair_deferred(p, S, row_block(p, row, k), defer)) return false;
+    return true;
+}
+constexpr int count_local(const Prototype &p)
+{
+    int c = 0;
+    for (int b = 0; b < p.n_blocks; ++b) c += blk_local(p.blk[b]) ? 1 : 0;
+    return c;
+}
+
+// How many of the thread's local edges leave their check message unfinished at the end of the check phase and finish it at the next
+// loop head, behind the early u reads (DEFER in the body).  Only the instantiations with early reads have that window.
+template <int CODE, int JW, int EARLY>
+constexpr int pair_defer_local()
+{
+    constexpr int nloc = 2 * count_local(*CODES[CODE].proto);
+    if (EARLY == 0) return 0;
+    if (LDPC_PAIR_DEFER_LOCAL >= 0) return LDPC_PAIR_DEFER_LOCAL < nloc ? LDPC_PAIR_DEFER_LOCAL : nloc;
+    return LDPC_PAIR_DEFER_LOCAL_F32 < nloc ? LDPC_PAIR_DEFER_LOCAL_F32 : nloc;
+}
+
 // FORM: the self-correction's form (Ops::self_correct): 0 = compare + select, 2 / 3 = the clamp forms
 // SOFT: the soft-output form (decode_ms_body's SOFT): the two adjacent marginals of a thread go to `app` as one store.
 // CORRECTED: normalized / offset min-sum (decode_ms_body's CORRECTED): m -> max(corr_scale * m - corr_offset, 0) on
@@ -121,7 +162,6 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     // frees the VCC round trips and two registers) the 20 % of LDS cycles lost to the 2-way conflicts of the 32-bit reads
     // show: 8.32-8.33 -> 8.43-8.45 M codewords/s, 2 spilled registers instead of 3 (profiles/r03_kbench/kb13.txt).
     constexpr bool ODD_B64 = LDPC_PAIR_ODD_B64 >= 0 ? LDPC_PAIR_ODD_B64 != 0 : true;
-    constexpr int LOCAL_IN_VAR = LDPC_PAIR_LOCAL_IN_VAR >= 0 ? LDPC_PAIR_LOCAL_IN_VAR : (std::is_same_v<T, float> ? 10 : 8);
     // HOIST: the nine wired addresses of the exchanged edges and the variable phase's own position depend on the thread and the
     // quarter body alone.  Formed per phase (the opaque `tq` of the phases below) they are 37 of the 290 full-rate VALU instructions
     // per wave and iteration of a VALU-bound loop: a shift per phase, an add and a mask per rotation read, and a v_or / v_add of
@@ -156,6 +196,25 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     // the verdict".
     constexpr int EARLY = pair_early_u<HOIST, NX>();
     static_assert(EARLY >= 0 && EARLY <= 15, "lgkmcnt counts to 15");
+    // DEFER: while the head waits for the verdict behind its EARLY reads, the VALU of the whole CU idles (all 16 waves stand at the
+    // same place, one LDS round trip behind a barrier), and directly on the other side of that barrier, in the VALU-bound end of the
+    // check phase where the slowest wave holds up the rest, sit instructions the barrier does not need: the last v_min3_f32 and the
+    // sign application of the LOCAL edges' check messages, which no other thread reads and whose first consumer is this thread's own
+    // variable phase, behind the verdict.  The first DEFER local edges (pair_defer_rank) leave them out of the check phase -- of the
+    // peeled pass too -- and the head finishes them between its last early read and the verdict's wait.  Kept across the barrier for
+    // that: the row's sign word per (row, index) with a deferred edge, and for a row of degree >= 4 the partial minimum over the other
+    // groups (exclusive_min_part) per group with one; the edge's own u register is free meanwhile, and v does not change between the
+    // check phase and the head.  The finished value is the same instruction on the same operands as exclusive_min's, so results are
+    // bit-identical.  On the exit path the finished values are dead (the epilogue reads va alone).  The instructions name neither a
+    // pending u pair nor the verdict (tests/test_pair_loop_head.py), and each result is pinned: left alone, the compiler sinks
+    // them below the exit branch, behind the wait (tests/test_pair_deferred_local.py).  Measurements: docs/experiments.md, "Pair
+    // kernel: local edges finished at the loop head".
+    constexpr int DEFER = pair_defer_local<CODE, JW, EARLY>();
+    static_assert(DEFER == 0 || (EARLY > 0 && !SOFT && !CORRECTED), "deferred local edges: the instantiations with early u reads");
+    // (with deferred edges the head's window and the variable phase's tail share one LDS-bound stretch, and the best split moved:
+    // re-swept together, LDPC_PAIR_LOCAL_IN_VAR_DEFER; the other instantiations keep their 10 / 8)
+    constexpr int LOCAL_IN_VAR = LDPC_PAIR_LOCAL_IN_VAR >= 0 ? LDPC_PAIR_LOCAL_IN_VAR
+                                 : DEFER > 0 ? LDPC_PAIR_LOCAL_IN_VAR_DEFER : (std::is_same_v<T, float> ? 10 : 8);
     constexpr bool PRIO_WAVES = true;            // LDPC_SETPRIO (decode_ms_kernel.hpp)
     (void)PRIO_WAVES;
 
@@ -189,6 +248,9 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     (void)fnext;
     ldpc_f2 upre[EARLY > 0 ? EARLY : 1];         // EARLY: the u pairs requested at the loop head, in the variable phase's order
     (void)upre;
+    int dsg[IPT][NROWS];                         // DEFER: the sign word of (index, row), for its deferred edges
+    R dx[IPT][NROWS][(NB + 2) / 3];              // DEFER: exclusive_min_part of (index, row, group of three), for its deferred edges
+    (void)dsg; (void)dx;
     T lraw[IPT][NTX];
 
     auto fetch_llrs = [&](uint32_t c) LDPC_INLINE {
@@ -307,6 +369,31 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
         constexpr int F = (FORM >= 2 && (BND || sizeof(T) <= 2)) ? FORM : (LDPC_PAIR_SELFCORR_CARRY != 0 ? 1 : 0);
         v[S][B] = O::template self_correct_b<BND, F>(nv, v[S][B]);                     // :422-425
     };
+
+    // DEFER: the check messages of the deferred local edges, from what the last check phase kept (see DEFER above)
+    auto finish_deferred = [&]() LDPC_INLINE {
+        static_for<0, NROWS>([&](auto R_) LDPC_INLINE {
+            constexpr int Rw = decltype(R_)::value;
+            constexpr int D = row_degree(P, Rw);
+            static_for<0, IPT>([&](auto S_) LDPC_INLINE {
+                constexpr int S = decltype(S_)::value;
+                R a[D];
+                static_for<0, D>([&](auto J_) LDPC_INLINE { a[decltype(J_)::value] = v[S][row_block(P, Rw, decltype(J_)::value)]; });
+                static_for<0, D>([&](auto J_) LDPC_INLINE {
+                    constexpr int J = decltype(J_)::value;
+                    constexpr int B = row_block(P, Rw, J);
+                    if constexpr (pair_deferred(P, S, B, DEFER)) {
+                        R xg = O::zero();
+                        if constexpr (exclusive_min_has_part<D>()) xg = dx[S][Rw][J / 3];
+                        const R e = exclusive_min_finish<O, D, true, J>(a, xg);
+                        u[S][B] = O::apply_sign(e, dsg[S][Rw], O::sign_word(v[S][B]));
+                        asm volatile("" : "+v"(u[S][B]));
+                    }
+                });
+            });
+        });
+    };
+    (void)finish_deferred;
 
     // ---- variable phase: marginals (decoder.rs:382-383, :408) -------------------------------------
     // FIRST_: iteration 0 peeled (LDPC_PAIR_PEEL_FIRST): u == 0 and v == 0, see decode_ms_kernel.hpp PEEL_FIRST
@@ -473,9 +560,26 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                         constexpr int J = decltype(J_)::value;
                         e[J] = __builtin_fmaxf(__fsub_rn(__fmul_rn(corr_scale, e[J]), corr_offset), 0.0f);
                     });
+                if constexpr (DEFER > 0) {
+                    // what finish_deferred() needs of this (index, row)
+                    bool any = false;
+                    static_for<0, D>([&](auto J_) LDPC_INLINE {
+                        constexpr int J = decltype(J_)::value;
+                        if constexpr (pair_deferred(P, S, row_block(P, Rw, J), DEFER)) {
+                            any = true;
+                            // (the first deferred edge of a group keeps the group's partial minimum)
+                            constexpr bool first = pair_defer_first_of_group(P, S, Rw, J, DEFER);
+                            if constexpr (exclusive_min_has_part<D>() && first) {
+                                dx[S][Rw][J / 3] = exclusive_min_part<O, D, true, CAP, J / 3>(a);
+                            }
+                        }
+                    });
+                    if (any) dsg[S][Rw] = sgn;
+                }
                 static_for<0, D>([&](auto J_) LDPC_INLINE {
                     constexpr int J = decltype(J_)::value;
                     constexpr int B = row_block(P, Rw, J);
+                    if constexpr (pair_deferred(P, S, B, DEFER)) return;                              // finish_deferred(), at the next loop head
                     u[S][B] = O::apply_sign(e[J], sgn, sr[J]);                         // :398-405
                     constexpr int slot = exch_slot(P, B);
                     if constexpr (slot >= 0) {
@@ -558,6 +662,11 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                         const int &base = vb[off < VB_HI ? 0 : 1];          // (an asm operand inside a generic lambda: a named reference)
                         asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(x) : "v"(base), "n"(off < VB_HI ? off : off - VB_HI));
                     });
+                    if constexpr (DEFER > 0) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        finish_deferred();
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fl) : "n"(EARLY));          // the verdict alone
                     if (__builtin_amdgcn_readfirstlane(fl) == 0) { done = true; ok = true; iters = it - 1; }   // :453-463
                     else if (it == maxiters) { done = true; }

@@ -12,7 +12,8 @@
     defined(LDPC_PAIR_ODD_B64) || defined(LDPC_PRIO_ROWS_PAIR) || defined(LDPC_SELFCORR_CARRY) || defined(LDPC_WAVE_VERDICT) || defined(LDPC_WG_VERDICT) || \
     defined(LDPC_PEEL_FIRST) || defined(LDPC_PAIR_PEEL_FIRST) || defined(LDPC_PAIR_FETCH_EARLY) || defined(LDPC_PAIR_SELFCORR_CARRY) || \
     defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH) || \
-    defined(LDPC_PAIR_HOIST) || defined(LDPC_PAIR_HOIST_F32) || defined(LDPC_PAIR_EARLY_U) || defined(LDPC_PAIR_EARLY_U_F32)
+    defined(LDPC_PAIR_HOIST) || defined(LDPC_PAIR_HOIST_F32) || defined(LDPC_PAIR_EARLY_U) || defined(LDPC_PAIR_EARLY_U_F32) || \
+    defined(LDPC_PAIR_DEFER_LOCAL) || defined(LDPC_PAIR_DEFER_LOCAL_F32) || defined(LDPC_PAIR_LOCAL_IN_VAR_DEFER)
 #error "the LDPC_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/)"
 #endif
 #endif
@@ -138,6 +139,22 @@
 #endif
 #ifndef LDPC_PAIR_EARLY_U_F32
 #define LDPC_PAIR_EARLY_U_F32 8
+#endif
+// How many of the thread's local edges (of 14 on TM8192, in the order of pair_defer_rank) finish their check message at the next
+// loop head, under the verdict's LDS round trip, instead of at the VALU-bound end of the check phase (DEFER in decode_ms_pair_body;
+// only the instantiations with early u reads have that window): LDPC_PAIR_DEFER_LOCAL -1 = per instantiation
+// (LDPC_PAIR_DEFER_LOCAL_F32 for the adopted ones), 0 = off, n = the first n.
+#ifndef LDPC_PAIR_DEFER_LOCAL
+#define LDPC_PAIR_DEFER_LOCAL -1
+#endif
+#ifndef LDPC_PAIR_DEFER_LOCAL_F32
+#define LDPC_PAIR_DEFER_LOCAL_F32 6
+#endif
+// LDPC_PAIR_LOCAL_IN_VAR of the instantiations that defer (the two settings were swept together on TM8192: K / LOCAL_IN_VAR 0/10 9.45,
+// 0/12 9.48, 0/14 9.50, 4/10 9.46, 4/12 9.37, 4/14 9.52, 5/12 9.55, 6/10 9.40, 6/12 9.65-9.68, 6/13 9.60, 6/14 9.55, 7/12 9.56,
+// 8/12 9.56, 8/14 9.45, 10/8 9.13, 10/10 9.18, 10/12 9.40, 11/10 9.09 M codewords/s; docs/experiments.md)
+#ifndef LDPC_PAIR_LOCAL_IN_VAR_DEFER
+#define LDPC_PAIR_LOCAL_IN_VAR_DEFER 12
 #endif
 
 // Wave priority over the six (check row, index) steps of the check phase; 3 before them.  A dozen
