@@ -8,8 +8,8 @@
 //     is one 64-bit LDS operation for both indices;
 //   * a pi_k block rotates a quarter by phi: the images of 2t and 2t+1 are adjacent, and when phi is
 //     EVEN they form an aligned pair -- one ds_read_b64 / ds_write_b64 and ONE address for both edges;
-//     for odd phi the two edges keep their 32-bit accesses (20 of the 32 (block, quarter) rotations of
-//     TM8192 are even);
+//     for odd phi the two marginals are read as halves of two aligned pairs and the two messages keep their
+//     32-bit stores (20 of the 32 (block, quarter) rotations of TM8192 are even);
 //   * both indices of a thread lie in the same quarter, so every rotation constant is a literal after
 //     one wave-uniform branch on the quarter (four copies of the body).
 // Everything else -- arithmetic, order of accumulation, exclusive minima, sign words, flags, persistent
@@ -22,10 +22,9 @@
 
 #include "decode_ms_kernel.hpp"
 
-// Tuned settings (LDPC_PAIR_*, LDPC_PRIO_ROWS_PAIR): decode_ms_tuning.hpp.
+// Tuned settings (LDPC_PAIR_*, LDPC_PRIO_ROWS_PAIR): decode_ms_tuning.hpp; what an instantiation makes of them: PairPlan.
 
 namespace ldpc {
-
 
 typedef float ldpc_f2 __attribute__((ext_vector_type(2)));
 
@@ -56,18 +55,6 @@ constexpr bool all_exchanged_are_pi(const Prototype &p)
     return true;
 }
 
-// Which instantiations keep their LDS addresses in registers across the iterations (HOIST in the body) instead of forming them
-// again in every phase: 0 = none of them, 1 = formed once per codeword (begin_codeword), 2 = once per kernel.  Adopted for the
-// hard-output f32 kernels (forms 2 and 3).  The soft, the corrected and the i8 / i16 instantiations keep the per-phase form and
-// their device code: none of them has been measured with the hoist (docs/experiments.md, "Pair kernel: LDS addresses out of the
-// iteration loop").
-template <class T, bool SOFT, bool CORRECTED>
-constexpr int pair_hoist_addresses()
-{
-    if (LDPC_PAIR_HOIST >= 0) return LDPC_PAIR_HOIST;
-    return (std::is_same_v<T, float> && !SOFT && !CORRECTED) ? LDPC_PAIR_HOIST_F32 : 0;
-}
-
 // The k-th exchange slot the variable phase reads (it walks the block columns in order, and a column's blocks in order), as a block
 // number; -1 past the last one.
 constexpr int pair_var_read_block(const Prototype &p, int k)
@@ -84,17 +71,7 @@ constexpr int pair_var_read_rank(const Prototype &p, int B)
     return -1;
 }
 
-// How many of the variable phase's exchanged-u reads the loop head issues before it has the verdict on the previous pass (EARLY in
-// the body).  Only the instantiations with hoisted addresses can: the reads go out on the hoisted bases.
-template <int HOIST, int NX>
-constexpr int pair_early_u()
-{
-    if (HOIST == 0 || LDPC_PAIR_PEEL_FIRST == 0) return 0;
-    if (LDPC_PAIR_EARLY_U >= 0) return LDPC_PAIR_EARLY_U < NX ? LDPC_PAIR_EARLY_U : NX;
-    return LDPC_PAIR_EARLY_U_F32 < NX ? LDPC_PAIR_EARLY_U_F32 : NX;
-}
-
-// Deferred local edges (DEFER in the body).  The order in which a thread's local edges are deferred: by check row, then index, then
+// Deferred local edges (PairPlan::DEFER).  The order in which a thread's local edges are deferred: by check row, then index, then
 // block -- the edges of one (row, index) share the one sign word that is kept for them, and are taken together.
 constexpr int pair_defer_rank(const Prototype &p, int S, int B)
 {
@@ -124,16 +101,98 @@ constexpr int count_local(const Prototype &p)
     return c;
 }
 
-// How many of the thread's local edges leave their check message unfinished at the end of the check phase and finish it at the next
-// loop head, behind the early u reads (DEFER in the body).  Only the instantiations with early reads have that window.
-template <int CODE, int JW, int EARLY>
-constexpr int pair_defer_local()
-{
-    constexpr int nloc = 2 * count_local(*CODES[CODE].proto);
-    if (EARLY == 0) return 0;
-    if (LDPC_PAIR_DEFER_LOCAL >= 0) return LDPC_PAIR_DEFER_LOCAL < nloc ? LDPC_PAIR_DEFER_LOCAL : nloc;
-    return LDPC_PAIR_DEFER_LOCAL_F32 < nloc ? LDPC_PAIR_DEFER_LOCAL_F32 : nloc;
-}
+// What one instantiation of decode_ms_pair_body is built with.  Each member depends on the ones above it alone: no early reads without
+// hoisted addresses, no deferral without early reads, deferral only on the hard-output, uncorrected f32 form.  The settings behind them
+// (LDPC_PAIR_*): decode_ms_tuning.hpp.
+template <int CODE, class T, bool SOFT, bool CORRECTED>
+struct PairPlan {
+    static constexpr int NX = PairGeometry<CODE, T>::NX;                        // exchanged u slots = u reads of a variable phase
+    static constexpr int NLOCAL = 2 * count_local(*CODES[CODE].proto);          // local edges of a thread
+    static constexpr int at_most(int want, int have) { return want < have ? want : have; }
+    // The adopted instantiations: the hard-output f32 kernels (forms 2 and 3).  The soft, the corrected and the i8 / i16 instantiations
+    // keep the per-phase addresses and their device code: none of them has been measured with the hoist (docs/experiments.md, "Pair
+    // kernel: LDS addresses out of the iteration loop").
+    static constexpr bool HARD_F32 = std::is_same_v<T, float> && !SOFT && !CORRECTED;
+
+    // HOIST: the LDS addresses of the loop stay in registers across the iterations (formed once per kernel, hoist_addresses() in the
+    // body) instead of being formed again in every phase.  The nine wired addresses of the exchanged edges and the variable phase's own
+    // position depend on the thread and the quarter body alone.  Formed per phase (the opaque `tq` of the body's phases) they are 37 of the 290 full-rate VALU instructions
+    // per wave and iteration of a VALU-bound loop: a shift per phase, an add and a mask per rotation read, and a v_or / v_add of
+    // 0x10000 for every block that lies past the 16-bit offset of a ds instruction (the compiler folds the block offsets it can
+    // see into the instructions and is left with those).  Hoisted, each address is formed once, carries the lds_bias() of its
+    // block and is made opaque, so that the compiler neither re-forms it per phase nor splits the block offset off it again:
+    // every access of the loop reaches its block through the instruction's offset alone, 253-257 VALU instructions per
+    // iteration.  The check phase held these registers over its whole length already (the u stores reuse the read addresses), so
+    // the loop's peak pressure does not move; see forget_llrs() for what the allocator parked in scratch around the loop at first.
+    // Measurements: docs/experiments.md, "Pair kernel: LDS addresses out of the iteration loop".
+    static constexpr bool HOIST = (LDPC_PAIR_HOIST >= 0 ? LDPC_PAIR_HOIST : HARD_F32 ? LDPC_PAIR_HOIST_F32 : 0) != 0;
+
+    // EARLY: how many of the variable phase's exchanged-u reads the loop head issues before it has the verdict on the previous pass.
+    // Only the instantiations with hoisted addresses can: the reads go out on the hoisted bases.
+    // The loop head tested the previous pass's verdict -- one LDS word, a full LDS round trip for every wave of the CU at the same
+    // moment, right behind a barrier and with nothing else resident -- and only then issued the variable phase's u reads: two round trips
+    // in series.  The u reads do not depend on the verdict (nobody writes a u slot before the next check phase, behind another barrier;
+    // on the exit path the epilogue ends with a barrier and the next codeword's peeled pass writes no u slot before its own), so the
+    // first EARLY of them go out right behind the verdict's read and the head waits for the verdict alone (lgkmcnt(EARLY): LDS returns
+    // in order).  The reads are inline asm -- as plain loads the compiler sinks them back below the branch -- so the compiler does not
+    // know that their destinations are pending.  What keeps that safe:
+    //   * continuing path: each pair is first touched by an asm that waits for it ("+v"), in front of its addition, with a count of its
+    //     own (the k-th is back once no more than EARLY - 1 - k operations are outstanding, whatever the compiler issued behind it), so
+    //     that the additions start while the later pairs are still on their way.  Nothing may use, copy or spill a pair between its
+    //     read and that wait;
+    //   * exit path: the pairs are dead there and their registers are reused (fetch_llrs writes VGPRs under vmcnt, which does not order
+    //     against a pending LDS return), so lgkmcnt is drained behind the loop, before the next codeword's LLR loads are issued, and
+    //     nothing on the way there may write one of those registers;
+    //     (both: tests/test_pair_loop_head.py walks every path from the head to the covering wait in the disassembly)
+    //   * a counted wait is sound for LDS alone: no scalar memory load may be outstanding at the head (there is none in the loops);
+    //   * a value out of an asm is divergent to the compiler: the verdict goes through readfirstlane so that the exit stays a scalar
+    //     branch and not an EXEC-masked region (decode_ms_launch.hpp on what those cost TM6144).
+    // Only loads move: va, the marginal stores and the local-edge updates stay behind the verdict (the epilogue needs the previous
+    // pass's va), and the order of the additions is unchanged.  Measurements: docs/experiments.md, "Pair kernel: the u reads ahead of
+    // the verdict".
+    // The drain: the loop leaves its head with u reads outstanding, whose destination registers are dead to the compiler and about to
+    // be reused.  (Drained behind iterate() and not in front of the `break`: an asm in the loop's exit block changes the shape of the
+    // loop, 844 spilled VGPRs.)  Nothing between the exit branch and that wait may write one of them.
+    // MAINTENANCE CONSTRAINT: the source cannot enforce that.  Between the loop's exit branch and the drain the compiler schedules
+    // what it likes (today: scalar moves, and in form 2 two v_mov_b32 of constants into other registers) into registers it
+    // believes free, the pending pairs' among them.  The only guard is tests/test_pair_loop_head.py, which walks the
+    // exit path in the disassembly of every loop of forms 2 and 3 and fails when an instruction there names a pending register.
+    // Any statement added between iterate() and the drain, any change to what the loop leaves live, and any compiler upgrade has to
+    // pass that test before it runs; if it cannot, set LDPC_PAIR_EARLY_U_F32 to 0 and leave the asm alone.
+    static constexpr int EARLY = !HOIST ? 0 : at_most(LDPC_PAIR_EARLY_U >= 0 ? LDPC_PAIR_EARLY_U : LDPC_PAIR_EARLY_U_F32, NX);
+    static_assert(EARLY >= 0 && EARLY <= 15, "lgkmcnt counts to 15");
+
+    // DEFER: how many of the thread's local edges leave their check message unfinished at the end of the check phase and finish it at
+    // the next loop head, behind the early u reads.  Only the instantiations with early reads have that window.
+    // While the head waits for the verdict behind its EARLY reads, the VALU of the whole CU idles (all 16 waves stand at the
+    // same place, one LDS round trip behind a barrier), and directly on the other side of that barrier, in the VALU-bound end of the
+    // check phase where the slowest wave holds up the rest, sit instructions the barrier does not need: the last v_min3_f32 and the
+    // sign application of the LOCAL edges' check messages, which no other thread reads and whose first consumer is this thread's own
+    // variable phase, behind the verdict.  The first DEFER local edges (pair_defer_rank) leave them out of the check phase -- of the
+    // peeled pass too -- and the head finishes them between its last early read and the verdict's wait.  Kept across the barrier for
+    // that: the row's sign word per (row, index) with a deferred edge, and for a row of degree >= 4 the partial minimum over the other
+    // groups (exclusive_min_part) per group with one; the edge's own u register is free meanwhile, and v does not change between the
+    // check phase and the head.  The finished value is the same instruction on the same operands as exclusive_min's, so results are
+    // bit-identical.  On the exit path the finished values are dead (the epilogue reads va alone).  The instructions name neither a
+    // pending u pair nor the verdict (tests/test_pair_loop_head.py), and each result is pinned: left alone, the compiler sinks
+    // them below the exit branch, behind the wait (tests/test_pair_deferred_local.py).  Measurements: docs/experiments.md, "Pair
+    // kernel: local edges finished at the loop head".
+    static constexpr int DEFER = EARLY == 0 ? 0 : at_most(LDPC_PAIR_DEFER_LOCAL >= 0 ? LDPC_PAIR_DEFER_LOCAL : LDPC_PAIR_DEFER_LOCAL_F32, NLOCAL);
+    static_assert(DEFER == 0 || (EARLY > 0 && HARD_F32), "deferred local edges: the instantiations with early u reads");
+
+    // LOCAL_IN_VAR: how many of the thread's local-edge updates run at the end of the variable phase instead of at the start of the
+    // check phase.  (With deferred edges the head's window and the variable phase's tail share one LDS-bound stretch, and the best split
+    // moved: re-swept together, LDPC_PAIR_LOCAL_IN_VAR_DEFER; the other instantiations keep their 10 / 8.)
+    static constexpr int LOCAL_IN_VAR = LDPC_PAIR_LOCAL_IN_VAR >= 0 ? LDPC_PAIR_LOCAL_IN_VAR
+                                        : DEFER > 0 ? LDPC_PAIR_LOCAL_IN_VAR_DEFER : (std::is_same_v<T, float> ? 10 : 8);
+
+    // FETCH_EARLY: where the next codeword's LLR loads are issued: before this one's epilogue (4-byte LLRs; the epilogue covers part of
+    // their latency) or at the top of its own turn (i8 / i16: the early loads' raw bytes are spilled across the epilogue at the
+    // 128-register budget -- which also waits for them on the spot -- 48 spilled registers against 3; fetching a column's two adjacent
+    // narrow LLRs with ONE load into ONE register halves what the early fetch keeps alive, and still spills 23 registers against 6:
+    // 8.00 -> 7.71, profiles/r03_kbench/kb22_pair_packed_fetch.txt).
+    static constexpr bool FETCH_EARLY = sizeof(T) >= 4;
+};
 
 // FORM: the self-correction's form (Ops::self_correct): 0 = compare + select, 2 / 3 = the clamp forms
 // SOFT: the soft-output form (decode_ms_body's SOFT): the two adjacent marginals of a thread go to `app` as one store.
@@ -156,80 +215,25 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     constexpr int N = CODES[CODE].n, NTX = N / M, NX = GEO::NX, NXC = GEO::NXC;
     constexpr int Q = M / 4, IPT = 2;
     constexpr int BLK_BYTES = M * 4, FLAG_OFF = (NX + NXC) * BLK_BYTES;
-    // odd rotations read their two marginals as halves of two aligned 64-bit pairs (see check_phase): +12 % for
-    // i8 (8.0 -> 9.0 M codewords/s).  For f32 the wider destinations cost nine spilled VGPRs in round 1 (6.7 -> 6.5) and
-    // nothing either way in round 2 (7.00 / 7.00); with round 3's shorter check phase (the clamp form of the self-correction
-    // frees the VCC round trips and two registers) the 20 % of LDS cycles lost to the 2-way conflicts of the 32-bit reads
-    // show: 8.32-8.33 -> 8.43-8.45 M codewords/s, 2 spilled registers instead of 3 (profiles/r03_kbench/kb13.txt).
-    constexpr bool ODD_B64 = LDPC_PAIR_ODD_B64 >= 0 ? LDPC_PAIR_ODD_B64 != 0 : true;
-    // HOIST: the nine wired addresses of the exchanged edges and the variable phase's own position depend on the thread and the
-    // quarter body alone.  Formed per phase (the opaque `tq` of the phases below) they are 37 of the 290 full-rate VALU instructions
-    // per wave and iteration of a VALU-bound loop: a shift per phase, an add and a mask per rotation read, and a v_or / v_add of
-    // 0x10000 for every block that lies past the 16-bit offset of a ds instruction (the compiler folds the block offsets it can
-    // see into the instructions and is left with those).  Hoisted, each address is formed once, carries the lds_bias() of its
-    // block and is made opaque, so that the compiler neither re-forms it per phase nor splits the block offset off it again:
-    // every access of the loop reaches its block through the instruction's offset alone, 253-257 VALU instructions per
-    // iteration.  The check phase held these registers over its whole length already (the u stores reuse the read addresses), so
-    // the loop's peak pressure does not move; see forget_llrs() for what the allocator parked in scratch around the loop at first.
-    // Measurements: docs/experiments.md, "Pair kernel: LDS addresses out of the iteration loop".
-    constexpr int HOIST = pair_hoist_addresses<T, SOFT, CORRECTED>();
-    // EARLY: the loop head tested the previous pass's verdict -- one LDS word, a full LDS round trip for every wave of the CU at the same
-    // moment, right behind a barrier and with nothing else resident -- and only then issued the variable phase's u reads: two round trips
-    // in series.  The u reads do not depend on the verdict (nobody writes a u slot before the next check phase, behind another barrier;
-    // on the exit path the epilogue ends with a barrier and the next codeword's peeled pass writes no u slot before its own), so the
-    // first EARLY of them go out right behind the verdict's read and the head waits for the verdict alone (lgkmcnt(EARLY): LDS returns
-    // in order).  The reads are inline asm -- as plain loads the compiler sinks them back below the branch -- so the compiler does not
-    // know that their destinations are pending.  What keeps that safe:
-    //   * continuing path: each pair is first touched by an asm that waits for it ("+v"), in front of its addition, with a count of its
-    //     own (the k-th is back once no more than EARLY - 1 - k operations are outstanding, whatever the compiler issued behind it), so
-    //     that the additions start while the later pairs are still on their way.  Nothing may use, copy or spill a pair between its
-    //     read and that wait;
-    //   * exit path: the pairs are dead there and their registers are reused (fetch_llrs writes VGPRs under vmcnt, which does not order
-    //     against a pending LDS return), so lgkmcnt is drained behind the loop, before the next codeword's LLR loads are issued, and
-    //     nothing on the way there may write one of those registers;
-    //     (both: tests/test_pair_loop_head.py walks every path from the head to the covering wait in the disassembly)
-    //   * a counted wait is sound for LDS alone: no scalar memory load may be outstanding at the head (there is none in the loops);
-    //   * a value out of an asm is divergent to the compiler: the verdict goes through readfirstlane so that the exit stays a scalar
-    //     branch and not an EXEC-masked region (decode_ms_launch.hpp on what those cost TM6144).
-    // Only loads move: va, the marginal stores and the local-edge updates stay behind the verdict (the epilogue needs the previous
-    // pass's va), and the order of the additions is unchanged.  Measurements: docs/experiments.md, "Pair kernel: the u reads ahead of
-    // the verdict".
-    constexpr int EARLY = pair_early_u<HOIST, NX>();
-    static_assert(EARLY >= 0 && EARLY <= 15, "lgkmcnt counts to 15");
-    // DEFER: while the head waits for the verdict behind its EARLY reads, the VALU of the whole CU idles (all 16 waves stand at the
-    // same place, one LDS round trip behind a barrier), and directly on the other side of that barrier, in the VALU-bound end of the
-    // check phase where the slowest wave holds up the rest, sit instructions the barrier does not need: the last v_min3_f32 and the
-    // sign application of the LOCAL edges' check messages, which no other thread reads and whose first consumer is this thread's own
-    // variable phase, behind the verdict.  The first DEFER local edges (pair_defer_rank) leave them out of the check phase -- of the
-    // peeled pass too -- and the head finishes them between its last early read and the verdict's wait.  Kept across the barrier for
-    // that: the row's sign word per (row, index) with a deferred edge, and for a row of degree >= 4 the partial minimum over the other
-    // groups (exclusive_min_part) per group with one; the edge's own u register is free meanwhile, and v does not change between the
-    // check phase and the head.  The finished value is the same instruction on the same operands as exclusive_min's, so results are
-    // bit-identical.  On the exit path the finished values are dead (the epilogue reads va alone).  The instructions name neither a
-    // pending u pair nor the verdict (tests/test_pair_loop_head.py), and each result is pinned: left alone, the compiler sinks
-    // them below the exit branch, behind the wait (tests/test_pair_deferred_local.py).  Measurements: docs/experiments.md, "Pair
-    // kernel: local edges finished at the loop head".
-    constexpr int DEFER = pair_defer_local<CODE, JW, EARLY>();
-    static_assert(DEFER == 0 || (EARLY > 0 && !SOFT && !CORRECTED), "deferred local edges: the instantiations with early u reads");
-    // (with deferred edges the head's window and the variable phase's tail share one LDS-bound stretch, and the best split moved:
-    // re-swept together, LDPC_PAIR_LOCAL_IN_VAR_DEFER; the other instantiations keep their 10 / 8)
-    constexpr int LOCAL_IN_VAR = LDPC_PAIR_LOCAL_IN_VAR >= 0 ? LDPC_PAIR_LOCAL_IN_VAR
-                                 : DEFER > 0 ? LDPC_PAIR_LOCAL_IN_VAR_DEFER : (std::is_same_v<T, float> ? 10 : 8);
-    constexpr bool PRIO_WAVES = true;            // LDPC_SETPRIO (decode_ms_kernel.hpp)
-    (void)PRIO_WAVES;
+    // HOIST, EARLY, DEFER, LOCAL_IN_VAR, FETCH_EARLY: PairPlan, with what each costs, buys and needs to stay safe
+    using PLAN = PairPlan<CODE, T, SOFT, CORRECTED>;
+    constexpr bool HOIST = PLAN::HOIST, FETCH_EARLY = PLAN::FETCH_EARLY;
+    constexpr int EARLY = PLAN::EARLY, DEFER = PLAN::DEFER, LOCAL_IN_VAR = PLAN::LOCAL_IN_VAR;
+    [[maybe_unused]] constexpr bool PRIO_WAVES = true;     // the name LDPC_SETPRIO tests (decode_ms_kernel.hpp): a pair codeword has 8 or 16 waves
 
     const int t = (int)(threadIdx.x & (M / 8 - 1)) + JW * (M / 8);
     __builtin_assume(t >= 0 && t < NT);
+    // (a copy of `batch` for the codeword loop and the queue, kept on purpose: with the parameter in its place the lambdas capture one
+    // variable less, and the soft-output f32 kernels come out with two VGPRs, the hard-output ones with two SGPR pairs, numbered the
+    // other way round -- docs/experiments.md, "The pair kernel without its refuted paths")
     const uint32_t n_groups = batch;
     uint32_t cw = blockIdx.x;
-    bool live = cw < batch;
-    (void)live;
 
     auto lds1 = [&](int off) LDPC_INLINE -> float & { return *reinterpret_cast<float *>(lds + off); };
     auto lds2 = [&](int off) LDPC_INLINE -> ldpc_f2 & { return *reinterpret_cast<ldpc_f2 *>(lds + off); };
     auto flag_at = [&](uint32_t which) LDPC_INLINE -> int & { return *reinterpret_cast<int *>(lds + FLAG_OFF + 4 * (which & 1)); };
     auto cap_flag = [&]() LDPC_INLINE -> int & { return *reinterpret_cast<int *>(lds + FLAG_OFF + 8); };
-    constexpr bool NOCAP_POSSIBLE = LDPC_PAIR_NOCAP && std::is_same_v<T, float>;
+    constexpr bool NOCAP_POSSIBLE = std::is_same_v<T, float>;
 
     // Rotation of block B for this body's quarter JW: phi, and where the even/odd split puts the edges.
     // Byte address (inside the block region, biased as in decode_ms_kernel.hpp) of the variable that check
@@ -300,12 +304,8 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                 static_assert(lds_xu_off(P, exch_slot(P, B), BLK_BYTES) - lo + 4 < 0x10000 && lds_xva_off(P, col_slot(P, P.blk[B].col), BLK_BYTES) - lo + 4 < 0x10000);
                 if constexpr (even_c(B)) {
                     had[0][B] = wire(B_, IC<0>{}, tb8);
-                } else if constexpr (ODD_B64) {
-                    had[0][B] = wire(B_, IC<-1>{}, tb8);
-                    had[1][B] = wire(B_, IC<1>{}, tb8);
-                    asm volatile("" : "+v"(had[1][B]));
                 } else {
-                    had[0][B] = wire(B_, IC<0>{}, tb8);
+                    had[0][B] = wire(B_, IC<-1>{}, tb8);
                     had[1][B] = wire(B_, IC<1>{}, tb8);
                     asm volatile("" : "+v"(had[1][B]));
                 }
@@ -322,10 +322,10 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     (void)own;
 
     auto begin_codeword = [&]() LDPC_INLINE {
-        if constexpr (HOIST == 1) hoist_addresses();
+        // (a copy of t, once the address of the exchange slots' zeroing that the peeled first pass made unnecessary: one v_mov_b32
+        // per codeword, kept so that every instantiation's device code stays what was measured)
         int tq = t;
-        asm volatile("" : "+v"(tq));             // opaque per phase (no address hoisting), but visibly a multiple of 8 below
-        const int tb8 = tq * 8;
+        asm volatile("" : "+v"(tq));
         static_for<0, IPT>([&](auto S_) LDPC_INLINE {
             constexpr int S = decltype(S_)::value;
             static_for<0, NB>([&](auto B_) LDPC_INLINE {
@@ -335,10 +335,6 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
             });
             static_for<0, NCOLS>([&](auto C_) LDPC_INLINE { va[S][decltype(C_)::value] = O::zero(); });
             static_for<0, NTX>([&](auto C_) LDPC_INLINE { llr[S][decltype(C_)::value] = O::load(lraw[S][decltype(C_)::value]); });
-        });
-        if constexpr (!LDPC_PAIR_PEEL_FIRST)
-        static_for<0, NX>([&](auto X_) LDPC_INLINE {                                   // u = 0 in every exchange slot
-            lds2(lds_xu_off(P, decltype(X_)::value, BLK_BYTES) + tb8) = ldpc_f2{0.0f, 0.0f};
         });
         if (t < 2) flag_at(t) = 0;
         // f32: the clamp of the exclusive minimum at FLT_MAX (decoder.rs:414-415) can only bite if some
@@ -366,7 +362,7 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
         // the clamp forms need a guarantee about the values: integer messages always have it, f32 only the codewords of the
         // clamp-free loop (they passed the range vote)
         constexpr bool BND = decltype(BND_)::value != 0;
-        constexpr int F = (FORM >= 2 && (BND || sizeof(T) <= 2)) ? FORM : (LDPC_PAIR_SELFCORR_CARRY != 0 ? 1 : 0);
+        constexpr int F = (FORM >= 2 && (BND || sizeof(T) <= 2)) ? FORM : 0;
         v[S][B] = O::template self_correct_b<BND, F>(nv, v[S][B]);                     // :422-425
     };
 
@@ -396,7 +392,7 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
     (void)finish_deferred;
 
     // ---- variable phase: marginals (decoder.rs:382-383, :408) -------------------------------------
-    // FIRST_: iteration 0 peeled (LDPC_PAIR_PEEL_FIRST): u == 0 and v == 0, see decode_ms_kernel.hpp PEEL_FIRST
+    // FIRST_: iteration 0, a pass of its own: u == 0 and v == 0, see decode_ms_kernel.hpp PEEL_FIRST
     auto variable_phase = [&](auto BND_, auto FIRST_) LDPC_INLINE {
         constexpr bool FIRST = decltype(FIRST_)::value != 0;
         constexpr bool PRE = EARLY > 0 && !FIRST;    // the loop head has requested the first EARLY u pairs (request_u_early)
@@ -456,6 +452,11 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
         });
     };
 
+    // An odd rotation's S = 0 message goes to the HIGH half of the aligned pair its first read address names.  (A constant of the body
+    // and not a literal in the store, on purpose: the store's lambdas capture it, as they captured the switch of the retired 32-bit form,
+    // and without that capture the hard-output f32 kernels come out with the loops' register copies in another order --
+    // docs/experiments.md, "The pair kernel without its refuted paths".)
+    constexpr bool ODD_S0_HIGH = true;
     // ---- check phase (decoder.rs:414-450 and :391-405 of the next iteration) -------------------------
     auto check_phase = [&](uint32_t it, auto CAP_, auto FIRST_) LDPC_INLINE {
         constexpr bool CAP = decltype(CAP_)::value != 0;
@@ -485,7 +486,7 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                     const ldpc_f2 xp = lds2(off + ad[0][B]);
                     xs[0][B] = O::from_lds(xp.x);
                     xs[1][B] = O::from_lds(xp.y);
-                } else if constexpr (ODD_B64) {
+                } else {
                     // odd phi: the two marginals are the HIGH half of one aligned pair and the LOW half of the next.
                     // Two ds_read_b64 of those pairs (2 LDS cycles each, conflict-free) instead of two
                     // ds_read_b32 whose 8-byte lane stride is a 2-way bank conflict (4 cycles each).
@@ -496,13 +497,6 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                     const ldpc_f2 lo = lds2(off + ad[0][B]), hi = lds2(off + ad[1][B]);
                     xs[0][B] = O::from_lds(lo.y);
                     xs[1][B] = O::from_lds(hi.x);
-                } else {
-                    if constexpr (HOIST == 0) {
-                        ad[0][B] = wire(B_, IC<0>{}, tb8);
-                        ad[1][B] = wire(B_, IC<1>{}, tb8);
-                    }
-                    xs[0][B] = O::from_lds(lds1(off + ad[0][B]));
-                    xs[1][B] = O::from_lds(lds1(off + ad[1][B]));
                 }
             }
         });
@@ -584,7 +578,7 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                     constexpr int slot = exch_slot(P, B);
                     if constexpr (slot >= 0) {
                         constexpr int off = lds_xu_off(P, slot, BLK_BYTES) - lds_bias(P, B, BLK_BYTES);
-                        if constexpr (!even_c(B)) lds1(off + ad[S][B] + (ODD_B64 && S == 0 ? 4 : 0)) = O::store(u[S][B]);
+                        if constexpr (!even_c(B)) lds1(off + ad[S][B] + (ODD_S0_HIGH && S == 0 ? 4 : 0)) = O::store(u[S][B]);
                         else if constexpr (S == 1) lds2(off + ad[0][B]) = ldpc_f2{O::store(u[0][B]), O::store(u[1][B])};
                     }
                 });
@@ -597,15 +591,8 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
 
     // ---- persistent loop over codewords ----------------------------------------------------------------
     if (t == 0) cap_flag() = 0;
-    if constexpr (HOIST == 2) hoist_addresses();
+    if constexpr (HOIST != 0) hoist_addresses();
     LDPC_SYNC();
-    // Where the next codeword's LLR loads are issued: before this one's epilogue (f32: 7.35 -> 7.66 M codewords/s, the
-    // epilogue covers part of their latency) or at the top of its own turn (i8 / i16: the early loads' raw bytes are
-    // spilled across the epilogue at the 128-register budget -- which also waits for them on the spot -- 48 spilled
-    // registers against 3, 6.99 -> 7.09; fetching a column's two adjacent narrow LLRs with ONE load into ONE register halves
-    // what the early fetch keeps alive, and still spills 23 registers against 6: 8.00 -> 7.71, profiles/r03_kbench/
-    // kb22_pair_packed_fetch.txt).  LDPC_PAIR_FETCH_EARLY: -1 = per type, 0 / 1 = force.
-    constexpr bool FETCH_EARLY = LDPC_PAIR_FETCH_EARLY >= 0 ? LDPC_PAIR_FETCH_EARLY != 0 : sizeof(T) >= 4;
     if (FETCH_EARLY && blockIdx.x < n_groups) fetch_llrs(blockIdx.x);
     // Dynamic distribution of the codewords (claim != nullptr): see decode_ms_body in decode_ms_kernel.hpp.  Thread 0
     // draws a ticket at the start of each decode; the codeword it names, gridDim.x + ticket, is this workgroup's NEXT
@@ -633,22 +620,20 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
         uint32_t iters = maxiters;
         // the iterations, as one loop per clamp mode (two check phases inside ONE loop cost 330 spilled VGPRs)
         auto iterate = [&](auto CAP_) LDPC_INLINE {
-            uint32_t it0 = 0;
-            if constexpr (LDPC_PAIR_PEEL_FIRST != 0) {
-                if (maxiters == 0) { done = true; return; }
-                variable_phase(IC<(decltype(CAP_)::value == 0 && NOCAP_POSSIBLE) ? 1 : 0>{}, IC<1>{});
-                LDPC_SYNC();
-                check_phase(0u, CAP_, IC<1>{});
-                collect_claim();
-                it0 = 1;
-            }
+            // iteration 0, a pass of its own (u = v = 0 folded, no exchange slot to zero)
+            if (maxiters == 0) { done = true; return; }
+            variable_phase(IC<(decltype(CAP_)::value == 0 && NOCAP_POSSIBLE) ? 1 : 0>{}, IC<1>{});
+            LDPC_SYNC();
+            check_phase(0u, CAP_, IC<1>{});
+            collect_claim();
             if constexpr (EARLY > 0) {
-                // (it0 == 1: the peeled build has no `it > 0` to test)
                 // fsel: the byte address of flag_at(it - 1), toggled once per pass and pinned to the scalar unit.  Derived from `it`
                 // and handed to an asm, the address pulls `it`, the cap test and both flag addresses into VGPRs in three of the four
                 // quarter bodies (v_add / v_and / v_xor / v_or with the flags' offset as a literal, per iteration).
+                // (`it` is declared in front of `fsel`: the other way round the two loop-carried scalars swap their SGPRs)
+                uint32_t it = 1;
                 int fsel = FLAG_OFF;
-                for (uint32_t it = 1;; ++it) {
+                for (;; ++it) {
                     asm volatile("" : "+s"(it));     // (pinned like fsel: the cap test stays an s_cmp, not a VGPR countdown)
                     LDPC_SYNC();
                     int fl, fa;                      // (fa: the address as a VGPR, kept for the store below -- no second v_mov_b32)
@@ -680,8 +665,10 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                     check_phase(it, CAP_, IC<0>{});
                 }
             } else
-            for (uint32_t it = it0;; ++it) {
-                if (it > 0) LDPC_SYNC();          // (the barrier before iteration 0 is taken below, before the clamp mode is read)
+            // (the `it > 0` tests stay: the compiler cannot rule out a 32-bit wrap of `it`, and without them the device code of every
+            // instantiation that runs this loop moves)
+            for (uint32_t it = 1;; ++it) {
+                if (it > 0) LDPC_SYNC();
                 if (it > 0 && flag_at(it - 1) == 0) { done = true; ok = true; iters = it - 1; }   // :453-463
                 else if (it == maxiters) { done = true; }
                 if (done) break;
@@ -689,25 +676,17 @@ LDPC_DEV void decode_ms_pair_body(const T *__restrict__ llrs, uint8_t *__restric
                 LDPC_SYNC();
                 if (it > 0 && t == 0) flag_at(it - 1) = 0;
                 check_phase(it, CAP_, IC<0>{});
-                if constexpr (LDPC_PAIR_PEEL_FIRST == 0) { if (it == 0) collect_claim(); }
             }
         };
-        LDPC_SYNC();                              // the zeroed exchange slots, the flags and the clamp vote are visible
+        LDPC_SYNC();                              // the flags and the clamp vote are visible
         if constexpr (NOCAP_POSSIBLE) {
             if (__builtin_amdgcn_readfirstlane(cap_flag()) != 0) iterate(IC<1>{});
             else iterate(IC<0>{});
         } else {
             iterate(IC<1>{});
         }
-        // EARLY: the loop left its head with u reads outstanding, whose destination registers are dead to the compiler and about to be
-        // reused.  (Drained here and not in front of the `break`: an asm in the loop's exit block changes the shape of the loop, 844
-        // spilled VGPRs.)  Nothing between the exit branch and this wait may write one of them.
-        // MAINTENANCE CONSTRAINT: the source cannot enforce that.  Between the loop's exit branch and this wait the compiler schedules
-        // what it likes (today: scalar moves, and in form 2 two v_mov_b32 of constants into other registers) into registers it
-        // believes free, the pending pairs' among them.  The only guard is tests/test_pair_loop_head.py, which walks the
-        // exit path in the disassembly of every loop of forms 2 and 3 and fails when an instruction there names a pending register.
-        // Any statement added between iterate() and this wait, any change to what the loop leaves live, and any compiler upgrade has to
-        // pass that test before it runs; if it cannot, set LDPC_PAIR_EARLY_U_F32 to 0 and leave the asm alone.
+        // EARLY: the drain of the u reads that the loop left outstanding.  MAINTENANCE CONSTRAINT (PairPlan::EARLY): no statement between
+        // iterate() and this wait without tests/test_pair_loop_head.py.
         if constexpr (EARLY > 0) {
             asm volatile("s_waitcnt lgkmcnt(0)");
             __builtin_amdgcn_sched_barrier(0);

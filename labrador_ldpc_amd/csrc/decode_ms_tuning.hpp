@@ -8,10 +8,9 @@
 
 #ifndef LDPC_TUNING_OVERRIDES_ALLOWED
 #if defined(LDPC_QUARTER_SPECIALISE) || defined(LDPC_NOCAP) || defined(LDPC_LOCAL_IN_VAR) || defined(LDPC_PRIO) || defined(LDPC_PRIO_ROWS) || \
-    defined(LDPC_PRIO_ROWS_LEAN) || defined(LDPC_PRIO_VAR) || defined(LDPC_TM2048_WAVES) || defined(LDPC_PAIR_LOCAL_IN_VAR) || defined(LDPC_PAIR_NOCAP) || \
-    defined(LDPC_PAIR_ODD_B64) || defined(LDPC_PRIO_ROWS_PAIR) || defined(LDPC_SELFCORR_CARRY) || defined(LDPC_WAVE_VERDICT) || defined(LDPC_WG_VERDICT) || \
-    defined(LDPC_PEEL_FIRST) || defined(LDPC_PAIR_PEEL_FIRST) || defined(LDPC_PAIR_FETCH_EARLY) || defined(LDPC_PAIR_SELFCORR_CARRY) || \
-    defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH) || \
+    defined(LDPC_PRIO_ROWS_LEAN) || defined(LDPC_PRIO_VAR) || defined(LDPC_TM2048_WAVES) || defined(LDPC_PAIR_LOCAL_IN_VAR) || \
+    defined(LDPC_PRIO_ROWS_PAIR) || defined(LDPC_SELFCORR_CARRY) || defined(LDPC_WAVE_VERDICT) || defined(LDPC_WG_VERDICT) || \
+    defined(LDPC_PEEL_FIRST) || defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH) || \
     defined(LDPC_PAIR_HOIST) || defined(LDPC_PAIR_HOIST_F32) || defined(LDPC_PAIR_EARLY_U) || defined(LDPC_PAIR_EARLY_U_F32) || \
     defined(LDPC_PAIR_DEFER_LOCAL) || defined(LDPC_PAIR_DEFER_LOCAL_F32) || defined(LDPC_PAIR_LOCAL_IN_VAR_DEFER)
 #error "the LDPC_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/)"
@@ -36,19 +35,6 @@
 #endif
 #ifndef LDPC_PAIR_SELFCORR_MED3
 #define LDPC_PAIR_SELFCORR_MED3 -1
-#endif
-// pair kernel: where the next codeword's LLR loads are issued
-#ifndef LDPC_PAIR_FETCH_EARLY
-#define LDPC_PAIR_FETCH_EARLY -1
-#endif
-// iteration 0 as a pass of its own on the pair kernel (u = v = 0 folded, no slot zeroing): TM8192 f32 7.51 -> 7.70,
-// i8 6.81 -> 7.02 M codewords/s.  (Round 1's version peeled only the variable phase and lost: 7.42 -> 6.94.)
-#ifndef LDPC_PAIR_PEEL_FIRST
-#define LDPC_PAIR_PEEL_FIRST 1
-#endif
-// the same select on the pair kernel (measured slower there: 7.25-7.40 against 7.50)
-#ifndef LDPC_PAIR_SELFCORR_CARRY
-#define LDPC_PAIR_SELFCORR_CARRY 0
 #endif
 // Codewords inside one wave (TC codes): barrier-free verdict at the top of the check phase, skipping the rest of the
 // phase on success (WAVE_VERDICT in the kernel body).
@@ -112,24 +98,14 @@
 #ifndef LDPC_PAIR_LOCAL_IN_VAR
 #define LDPC_PAIR_LOCAL_IN_VAR -1
 #endif
-// f32: run the check phase without the FLT_MAX clamp of the exclusive minimum when no LLR of the codeword
-// exceeds the launch's nocap_limit in magnitude (see begin_codeword): 6.84 -> 7.05.
-#ifndef LDPC_PAIR_NOCAP
-#define LDPC_PAIR_NOCAP 1
-#endif
-// Odd rotations read their two marginals as halves of two aligned 64-bit pairs: -1 = the default (on: i8/i16 8.0 -> 9.0 in
-// round 1; f32 7.05 -> 6.90 then, 8.33 -> 8.44 with round 3's check phase), 0 / 1 = force.
-#ifndef LDPC_PAIR_ODD_B64
-#define LDPC_PAIR_ODD_B64 -1
-#endif
 // LDS addresses of the loop (the exchanged edges' wired addresses, the variable phase's own position) kept in registers across the
-// iterations: LDPC_PAIR_HOIST -1 = per instantiation (pair_hoist_addresses(): the hard-output f32 kernels), 0 / 1 / 2 = force for
-// every instantiation (off / formed per codeword / formed per kernel); LDPC_PAIR_HOIST_F32 = the mode of the adopted instantiations.
+// iterations: LDPC_PAIR_HOIST -1 = per instantiation (PairPlan::HOIST: the hard-output f32 kernels), 0 / 1 = force for every
+// instantiation (off / on: formed once per kernel); LDPC_PAIR_HOIST_F32 = 0 / 1 for the adopted instantiations.
 #ifndef LDPC_PAIR_HOIST
 #define LDPC_PAIR_HOIST -1
 #endif
 #ifndef LDPC_PAIR_HOIST_F32
-#define LDPC_PAIR_HOIST_F32 2
+#define LDPC_PAIR_HOIST_F32 1
 #endif
 // How many of the variable phase's exchanged-u reads the loop head issues before it has the previous pass's verdict (EARLY in
 // decode_ms_pair_body; only the instantiations with hoisted addresses can): LDPC_PAIR_EARLY_U -1 = per instantiation
