@@ -38,20 +38,24 @@
 //    first (Geo::COL_ORDER); a row's running state starts with its first edge (no all-ones initial state, no compare for that
 //    edge) and REPLACES the row's old state the moment its last edge is done, so that old and new state of a row are live together
 //    only between its first and its last edge.  Hard decisions live in LDS where that frees the registers for one more wave per
-//    SIMD (Geo::HARD_LDS).
+//    SIMD (BsPlan::HARD_LDS).
 //
 //  * WHAT AN INSTRUCTION COSTS (round 5, profiles/r05_kbench/permute_pipeline.txt).  At two waves per SIMD a wave is bound by ISSUE
 //    -- one instruction of any kind per ~4.6 cycles, plus ~3.9 ns of SIMD time per ds_bpermute -- so the loop is written to issue
 //    few: the next permutation job's eight ds_bpermute are in flight behind the current job's arithmetic, which lets ONE s_waitcnt
-//    per job replace eight counted ones (Geo::PIPE); an exchanged edge's (sign, magnitude ^ sign) planes are kept from the variable
-//    side for the check side (Geo::KEEP); the check side never forms the saturated va (-sat) u, it forms that value's KEY from the
+//    per job replace eight counted ones (BsPlan::PIPE); an exchanged edge's (sign, magnitude ^ sign) planes are kept from the variable
+//    side for the check side (BsPlan::KEEP); the check side never forms the saturated va (-sat) u, it forms that value's KEY from the
 //    wrapped difference and the overflow flag (Decoder::columns); a row's second edge needs one compare (min2 is still the largest
-//    key); TM1280 rotates lanes with a DPP quad_perm instead of ds_bpermute (Geo::QUAD).
+//    key); TM1280 rotates lanes with a DPP quad_perm instead of ds_bpermute (BsPlan::QUAD).
+//
+// What an instantiation is built with -- the members named above, per code, with what each was measured at -- stands in BsPlan
+// (decode_ms_bs_plan.hpp); the settings behind it (BS_*) in decode_ms_tuning.hpp.
 #pragma once
 
 #include <cstdint>
 
 #include "codes.hpp"
+#include "decode_ms_bs_plan.hpp"
 
 #ifndef BS_FN
 #if defined(__HIPCC__)
@@ -107,12 +111,8 @@ static_assert(TT_XOR3 == 0x96 && TT_MAJ == 0xE8 && TT_MUX == 0xCA && TT_OR3 == 0
 
 constexpr int ilog2c(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
 
-// Bit planes of a message / marginal (two's complement).  8 = i8, what the library ships.  Everything below is written for PL planes: a
-// build with -DBS_PLANES=16 decodes with i16 saturation (the experiment behind DESIGN.md section 7: sign-extended i8 LLRs through the
-// i8 loader, checked against the i16 oracle in tests/test_bitslice_emu.py) -- twice the instructions and registers per edge.
-#ifndef BS_PLANES
-#define BS_PLANES 8
-#endif
+// Bit planes of a message / marginal (two's complement): BS_PLANES (decode_ms_tuning.hpp), 8 = i8, what the library ships.  Everything
+// below is written for PL planes.
 inline constexpr int PL = BS_PLANES, MG = PL - 1;          // planes of a value, of a magnitude
 inline constexpr int LLRP = 8;                             // planes of an LLR as the (i8) loader delivers it
 static_assert(PL == 8 || PL == 16);
@@ -123,6 +123,7 @@ static_assert(PL == 8 || PL == 16);
 // counts edges, exchanged edges or transmitted columns then counts the OWNED ones.
 template <int CODE, int HALF = -1>
 struct Geo {
+    using PLAN = BsPlan<CODE>;                      // what the code's kernels are built with, and why
     static constexpr Prototype P = *CODES[CODE].proto;
     static constexpr int M = CODES[CODE].m, N = CODES[CODE].n, NP = N + CODES[CODE].p;
     static constexpr int Q = M / 4;                 // indices per quarter
@@ -263,19 +264,9 @@ struct Geo {
     }
     static constexpr Jobs JOBS = jobs();
     static constexpr int job_of(int e, int side) { for (int j = 0; j < JOBS.n; ++j) if (JOBS.edge[j] == e && JOBS.side[j] == side) return j; return -1; }
-#ifndef BS_PIPE
-#define BS_PIPE 3
-#endif
-    // bit 0: the two-wave kernels, bit 1: rate 2/3, bit 2: rate 1/2 (which has no registers for it: 21-23 spilled values, -3 %).
-    // What it buys is not hidden latency -- the SIMD's other wave hid that already -- but ONE s_waitcnt per job instead of one per
-    // plane: a job's results have long arrived when they are collected (profiles/r05_kbench/permute_pipeline.txt: +1.2 ... +1.9 %).
-    // M = 128 (TM1280): a quarter is ONE lane and a codeword one quad of lanes, so the lane permutation of a pi_k block is a rotation of
-    // the quad by theta_k -- a DPP quad_perm on a v_mov_b32 (no LDS, no latency; nothing at all for theta_k = 0) instead of a
-    // ds_bpermute_b32, which at two waves per SIMD costs the SIMD ~4.4 x a VALU instruction (profiles/r04_kbench/sdwa_rate.txt).
-#ifndef BS_QUAD
-#define BS_QUAD 1
-#endif
-    static constexpr bool QUAD = W == 4 && BS_QUAD;
+    // the lane permutation of a pi_k block as a DPP quad_perm (TM1280: a codeword is one quad of lanes) and its control word
+    static constexpr bool QUAD = PLAN::QUAD;
+    static_assert(!QUAD || W == 4);
     static constexpr int quad_ctrl(int e, int side)
     {
         const int th = theta_of(P.blk[e].val);
@@ -283,7 +274,7 @@ struct Geo {
         for (int i = 0; i < 4; ++i) c |= ((side == 0 ? i - th : i + th) & 3) << (2 * i);
         return c;
     }
-    static constexpr bool PIPE = ((SPLIT ? 1 : P.n_blocks > 20 ? 2 : 4) & BS_PIPE) != 0 && !QUAD;
+    static constexpr bool PIPE = PLAN::PIPE;
     // job j + 1 is issued before job j's results are used
     static constexpr bool issues_next(int j)
     {
@@ -291,48 +282,15 @@ struct Geo {
         return JOBS.side[j + 1] == 0 || (JOBS.side[j] == 1 && P.blk[JOBS.edge[j]].col == P.blk[JOBS.edge[j + 1]].col);
     }
     static constexpr bool issued_early(int j) { return j > 0 && issues_next(j - 1); }
-    // An exchanged edge's u is needed twice, at check alignment: permuted into the marginal (variable side) and subtracted from the
-    // permuted marginal (check side).  For the first KEEP exchanged edges of a block column the (sign, magnitude ^ sign) planes formed
-    // for the variable side are KEPT for the check side instead of formed again (the seven XORs and whatever of the row-state multiplexer
-    // the compiler did not carry over by itself; the registers exist: the kept planes die at the start of the check side, before its peak).
-    // Measured +0.4 ... +2 % on every code (profiles/r05_kbench/permute_pipeline.txt).
-#ifndef BS_KEEP_SPLIT
-#define BS_KEEP_SPLIT 3
-#endif
-#ifndef BS_KEEP_R23
-#define BS_KEEP_R23 3
-#endif
-#ifndef BS_KEEP_R12
-#define BS_KEEP_R12 3
-#endif
-    static constexpr int KEEP = SPLIT ? BS_KEEP_SPLIT : P.n_blocks > 20 ? BS_KEEP_R23 : BS_KEEP_R12;
+    // the first KEEP exchanged edges of a block column keep their (sign, magnitude ^ sign) planes from the variable side for the check side
+    static constexpr int KEEP = PLAN::KEEP;
     static constexpr int keep_rank(int e) { int s = 0; for (int i = 0; i < e; ++i) s += (owns(i) && !local(i) && P.blk[i].col == P.blk[e].col) ? 1 : 0; return s; }
     static constexpr bool kept(int e) { return owns(e) && !local(e) && keep_rank(e) < KEEP; }
     static constexpr int LLR_WORDS = NTX_OWN * LLRP * 64;          // words of LLR planes per wave
-    // the rate-4/5 codes (39 edges: 218 planes of state before any temporary) exist only in the two-waves-per-group form
-    static constexpr bool TWO_WAVES = P.n_blocks > 30;
-    // Every state update of the rate-2/3 codes is pinned to its place in the program (Decoder::pin_update): without that the
-    // instruction selector's data-flow order keeps values whose next use is an iteration away live to the end of the block.  The
-    // rate-1/2 codes fit their registers without the pins and run 6 % faster with the freedom (TM8192 16.9 against 15.9 M codewords/s);
-    // the two-wave form of the rate-4/5 codes measured 36.8 (no pins) against 36.3 / 34.4 (profiles/r04_kbench/split_rate.txt).
-#ifndef BS_PINNED_R12
-#define BS_PINNED_R12 0
-#endif
-#ifndef BS_PINNED_R23
-#define BS_PINNED_R23 1
-#endif
-#ifndef BS_PINNED_SPLIT
-#define BS_PINNED_SPLIT 0
-#endif
-    // bit 0: the state updates, bit 1: the uses of the old row state in edge_u, bit 2: the magnitudes of a finished row
-    static constexpr int PINNED = SPLIT ? BS_PINNED_SPLIT : P.n_blocks > 20 ? BS_PINNED_R23 : BS_PINNED_R12;
-    // Hard decisions in LDS instead of one register per block column (one ds_write per column and iteration; a read as well where a
-    // wave holds several codewords, whose finished ones keep their decisions): the rate-1/2 codes, which that brings under the 168
-    // registers of three waves per SIMD.
-#ifndef BS_HARD_LDS
-#define BS_HARD_LDS 1
-#endif
-    static constexpr bool HARD_LDS = !SPLIT && P.n_blocks <= 20 && BS_HARD_LDS;
+    static constexpr bool TWO_WAVES = PLAN::TWO_WAVES;                          // the code's kernels take two waves per group (SPLIT: this is one)
+    static constexpr bool PINNED = PLAN::PINNED;                                // state updates pinned to their place (Decoder::pin_update)
+    static constexpr bool HARD_LDS = PLAN::HARD_LDS && !SPLIT;                  // hard decisions in LDS, not in a register per block column
+                                                                                // (a half keeps its own in registers: SplitGroup::epilogue)
     static constexpr int ROW_NEW = 2 * PL + 2 + ARG;                           // planes of a row's running state: two keys, sign, parity, arg-min
     // LDS of a wave: lane permutations of the exchanged blocks [NX][2 directions][64] as 16-bit entries (source lane address | rotate
     // amount << 8; constant for the kernel's lifetime), hard-decision words [NCOLS][64] -- which double as the staging slab (STAGE_BYTES)
@@ -341,14 +299,9 @@ struct Geo {
     // (dead by then) and the staging slab is the wave's exchange buffer, which lies behind both private areas (SplitLayout).
     static constexpr int LDS_PERM = 0, LDS_PERM_END = LDS_PERM + NX * 2 * 64 * 2;
     static constexpr int HARD_BYTES = NCOLS_OWN * 256 > 2304 ? NCOLS_OWN * 256 : 2304;             // (>= STAGE_BYTES, a multiple of 256)
-    // Rate 1/2 (three waves per SIMD, 168 registers): the "v != 0" plane of the first NZ_LDS edges lives in LDS -- read once and written
-    // once per iteration, at the edge's check side -- in the part of the staging slab that the hard-decision words leave free during
-    // the iterations: four planes the register allocator would otherwise keep in scratch (spilled values 11/14 -> 8/10; TM8192 i8
-    // +2...+3.5 %, TM2048 +1.5 %).  More than the slab holds costs a wave per CU: 6 planes -3 % (profiles/r05_kbench/spill_leak.txt).
-#ifndef BS_NZ_LDS
-#define BS_NZ_LDS 4
-#endif
-    static constexpr int NZ_LDS = HARD_LDS ? BS_NZ_LDS : 0;
+    // the "v != 0" plane of the first NZ_LDS edges lives in LDS: in the part of the staging slab that the hard-decision words leave free
+    // during the iterations (NZ_IN_SLAB), the rest behind the wave's private area
+    static constexpr int NZ_LDS = HARD_LDS ? PLAN::NZ_LDS : 0;
     static constexpr int NZ_IN_SLAB = (HARD_BYTES - NCOLS_OWN * 256) / 256 < NZ_LDS ? (HARD_BYTES - NCOLS_OWN * 256) / 256 : NZ_LDS;
     static constexpr int nz_slot(int e) { int s = 0; for (int i = 0; i < e; ++i) s += owns(i) ? 1 : 0; return s; }       // ordinal among the owned edges
     static constexpr bool nz_in_lds(int e) { return owns(e) && nz_slot(e) < NZ_LDS; }
@@ -475,39 +428,11 @@ struct Decoder {
 
     BS_FN V hard_addr(int c) const { return B::add(B::shl(lane, 2), B::c(GEO::LDS_HARD + GEO::col_slot(c) * 256)); }
 
-    BS_FN void reset_state(B &b)
+    // decoder.rs:374: the working area is zeroed, so before iteration 0 min1 = min2 = 0, every v = 0, every sign product +.
+    // z(x) zeroes a state register, zl(addr) a state word in LDS
+    template <class Z, class ZL>
+    BS_FN void reset_with(Z z, ZL zl)
     {
-        // decoder.rs:374: the working area is zeroed, so before iteration 0 min1 = min2 = 0, every v = 0, every sign product +
-        sfor<0, NROWS>([&](auto R_) {
-            constexpr int r = decltype(R_)::value;
-            if constexpr (GEO::has_row(r)) {
-                sfor<0, MG>([&](auto K_) { constexpr int k = decltype(K_)::value; m1[r][k] = B::c(0); m2[r][k] = B::c(0); });
-                S[r] = B::c(0);
-                sfor<0, ARG>([&](auto K_) { arg[r][decltype(K_)::value] = B::c(0); });
-            }
-        });
-        sfor<0, NB>([&](auto E_) {
-            constexpr int e = decltype(E_)::value;
-            if constexpr (GEO::owns(e)) {
-                sv[e] = B::c(0);
-                if constexpr (GEO::nz_in_lds(e)) b.lds_write32(B::add(B::shl(lane, 2), B::c(GEO::nz_addr(e))), B::c(0));
-                else nz[e] = B::c(0);
-            }
-        });
-        sfor<0, NCOLS>([&](auto C_) {
-            constexpr int c = decltype(C_)::value;
-            if constexpr (GEO::owns_col(c)) {
-                if constexpr (GEO::HARD_LDS) b.lds_write32(hard_addr(c), B::c(0));        // (max_iters = 0: all-zero output, decoder.rs:466-473)
-                else hard[c] = B::c(0);
-            }
-        });
-    }
-
-    // the same for the lanes of `fresh` only (slot refill, decode_refill below): they start a codeword, the other lanes keep theirs
-    BS_FN void reset_state(B &b, uint64_t fresh)
-    {
-        auto z = [&](V &x) { x = B::select_lanes(fresh, B::c(0), x); };
-        const V fp = b.plane_of(fresh);
         sfor<0, NROWS>([&](auto R_) {
             constexpr int r = decltype(R_)::value;
             if constexpr (GEO::has_row(r)) {
@@ -520,17 +445,24 @@ struct Decoder {
             constexpr int e = decltype(E_)::value;
             if constexpr (GEO::owns(e)) {
                 z(sv[e]);
-                if constexpr (GEO::nz_in_lds(e)) b.lds_write32_if(B::add(B::shl(lane, 2), B::c(GEO::nz_addr(e))), B::c(0), fp);
+                if constexpr (GEO::nz_in_lds(e)) zl(B::add(B::shl(lane, 2), B::c(GEO::nz_addr(e))));
                 else z(nz[e]);
             }
         });
         sfor<0, NCOLS>([&](auto C_) {
             constexpr int c = decltype(C_)::value;
             if constexpr (GEO::owns_col(c)) {
-                if constexpr (GEO::HARD_LDS) b.lds_write32_if(hard_addr(c), B::c(0), fp);
+                if constexpr (GEO::HARD_LDS) zl(hard_addr(c));        // (max_iters = 0: all-zero output, decoder.rs:466-473)
                 else z(hard[c]);
             }
         });
+    }
+    BS_FN void reset_state(B &b) { reset_with([](V &x) { x = B::c(0); }, [&](V at) { b.lds_write32(at, B::c(0)); }); }
+    // the same for the lanes of `fresh` only (slot refill, decode_refill below): they start a codeword, the other lanes keep theirs
+    BS_FN void reset_state(B &b, uint64_t fresh)
+    {
+        const V fp = b.plane_of(fresh);
+        reset_with([&](V &x) { x = B::select_lanes(fresh, B::c(0), x); }, [&](V at) { b.lds_write32_if(at, B::c(0), fp); });
     }
 
     // "this edge holds the row's min1": arg[r] == slot.  An AND over ARG literals (plane k, or its complement where bit k of SLOT is 0):
@@ -566,10 +498,6 @@ struct Decoder {
     BS_FN void edge_u(V &su, V (&mg)[MG])
     {
         constexpr int r = GEO::P.blk[E].row, slot = GEO::slot_of(E);
-        // (everything below depends on the OLD row state only, which exists from the top of the iteration: without the pins the
-        // instruction selector computes later edges' u early and keeps it)
-        sfor<0, ARG>([&](auto K_) { pin_use(arg[r][decltype(K_)::value]); });
-        pin_use(S[r]);
         const V sel = is_arg<r, slot>();
         sfor<0, MG>([&](auto K_) { constexpr int k = decltype(K_)::value; mg[k] = op3<TT_MUX>(sel, m2[r][k], m1[r][k]); });
         su = B::xor_(S[r], sv[E]);
@@ -609,9 +537,7 @@ struct Decoder {
         amt = B::add(phi, over);                                                  // rotr by phi + wrap
     }
 
-    static BS_FN void pin_update(V &x) { if constexpr (GEO::PINNED & 1) B::pin(x); }
-    static BS_FN void pin_use(V &x) { if constexpr (GEO::PINNED & 2) B::pin(x); }
-    static BS_FN void pin_row(V &x) { if constexpr (GEO::PINNED & 4) B::pin(x); }
+    static BS_FN void pin_update(V &x) { if constexpr (GEO::PINNED) B::pin(x); }
 
     template <int IDX> BS_FN V perm_entry(B &b) const { return b.lds_read_u16(B::add(B::shl(lane, 1), B::c(GEO::LDS_PERM + IDX * 128))); }
     // The entries are used in a fixed order (Geo::PERM_ORDER), so each use hands out the entry read during the PREVIOUS use and starts
@@ -696,9 +622,6 @@ struct Decoder {
         to_mag(W2[R], m2[R]);
         S[R] = Sn[R];
         sfor<0, ARG>([&](auto K_) { constexpr int k = decltype(K_)::value; arg[R][k] = argn[R][k]; });
-        // (the magnitudes are formed HERE: left to the instruction selector, their last XORs sink to their first use in the next
-        // iteration and keys and carries -- 24 planes instead of 14 -- stay live until then)
-        sfor<0, MG>([&](auto K_) { constexpr int k = decltype(K_)::value; pin_row(m1[R][k]); pin_row(m2[R][k]); });
         fail = B::or_(fail, Pn[R]);                                                   // non-zero bits = unsatisfied checks (:453)
     }
 
@@ -942,8 +865,12 @@ BS_FN void gather_planes(B &b, typename B::V p0, int stage, typename B::V (&X)[8
     stage_t(IC<1>{}, 0x55555555u);
 }
 
+// the lanes of codeword (slot) g of a wave that holds 64 / W codewords, as a lane mask
+constexpr uint64_t slot_lanes(int W, int g) { return (W == 64 ? ~0ull : ((1ull << (W & 63)) - 1)) << ((g * W) & 63); }
+
 // the hard-decision plane of one block column (64 words at LDS offset `base`, one per lane) -> the lane's dword of 32 consecutive
-// output bits, MSB first inside each byte (decoder.rs:455-461)
+// output bits, MSB first inside each byte (decoder.rs:455-461).  (emit_slot and SplitGroup::emit_owned carry the same loop over the
+// L words of a quarter: as one shared function it compiled to other code in both slot-refill kernels, docs/experiments.md.)
 template <int CODE, class B, class D>
 BS_FN typename B::V pack_hard_column(B &b, const D &d, int base)
 {
@@ -1020,7 +947,7 @@ BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint3
         const uint64_t unsat_lanes = b.ballot(fail);
         sfor<0, G>([&](auto G_) {
             constexpr int g = decltype(G_)::value;
-            constexpr uint64_t gm = (W == 64 ? ~0ull : ((1ull << (W & 63)) - 1)) << ((g * W) & 63);
+            constexpr uint64_t gm = slot_lanes(W, g);
             if (!(unsat_lanes & gm) && !(frozen_mask & gm)) {                  // satisfied for the first time: (true, it)  (:453-463)
                 iters_s[g] = it;
                 ok_mask |= gm;
@@ -1031,8 +958,7 @@ BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint3
     V iters_v = B::c(iters_s[0]);
     sfor<1, G>([&](auto G_) {
         constexpr int g = decltype(G_)::value;
-        constexpr uint64_t gm = ((1ull << (W & 63)) - 1) << ((g * W) & 63);
-        iters_v = B::select_lanes(gm, B::c(iters_s[g]), iters_v);
+        iters_v = B::select_lanes(slot_lanes(W, g), B::c(iters_s[g]), iters_v);
     });
     const V ok_v = B::and_(b.plane_of(ok_mask), B::c(1));
 
@@ -1073,7 +999,7 @@ BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint3
 // Frames are wave-uniform scalars, so a slot's global addresses are a scalar base plus a lane offset whatever the batch size.
 template <int G, int W>
 struct Slots {
-    static constexpr uint64_t gm(int g) { return (W == 64 ? ~0ull : ((1ull << (W & 63)) - 1)) << ((g * W) & 63); }      // the lanes of slot g
+    static constexpr uint64_t gm(int g) { return slot_lanes(W, g); }
     uint64_t active = 0;                   // lanes of the slots with a codeword in progress
     uint64_t fin = ~0ull, ok = 0;          // lanes of the slots that are finished (initially: all are to be filled); of those, the successes
     uint32_t it[G], fr[G];                 // iterations done, frame per slot
@@ -1143,11 +1069,7 @@ template <int CODE> struct SlotLoad {
     using GEO = Geo<CODE>;
     static constexpr int M = GEO::M, N = GEO::N, W = GEO::W;
     static constexpr int SLAB_FREE = GEO::NZ_IN_SLAB > 0 ? GEO::NCOLS * 256 : GEO::HARD_BYTES;
-#ifdef BS_REFILL_PIECE
-    static constexpr int PIECE = (N % BS_REFILL_PIECE == 0 && BS_REFILL_PIECE % M == 0) ? BS_REFILL_PIECE : N;
-#else
     static constexpr int PIECE = (N + 16 * (N / 256) <= SLAB_FREE) ? N : 1024;      // bytes staged at a time
-#endif
     static_assert(PIECE % M == 0 && N % PIECE == 0 && PIECE % 16 == 0 && PIECE + 16 * (PIECE / 256) <= SLAB_FREE, "a piece is whole block columns and fits the slab");
     static constexpr int COLS = PIECE / M, UNITS = COLS * W;                         // block columns and (column, lane) units per piece
     static constexpr int ROUNDS = (PIECE + 1023) / 1024, PIECES = N / PIECE;        // 16-byte loads per lane and piece; pieces

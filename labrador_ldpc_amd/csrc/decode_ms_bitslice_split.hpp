@@ -200,7 +200,7 @@ struct SplitGroup {
         const uint64_t unsat_lanes = b.ballot(fail);
         sfor<0, G>([&](auto G_) {
             constexpr int g = decltype(G_)::value;
-            constexpr uint64_t gm = (W == 64 ? ~0ull : ((1ull << (W & 63)) - 1)) << ((g * W) & 63);
+            constexpr uint64_t gm = slot_lanes(W, g);
             if (!(unsat_lanes & gm) && !(frozen_mask & gm)) {                  // satisfied for the first time: (true, it)
                 iters_s[g] = it;
                 ok_mask |= gm;
@@ -214,12 +214,12 @@ struct SplitGroup {
     {
         sfor<0, NCOLS>([&](auto C_) {
             constexpr int c = decltype(C_)::value;
-            if constexpr (GEO::owns_col(c)) b.lds_write32(B::add(B::shl(lane, 2), B::c(GEO::LDS_HARD + c_slot(c) * 256)), d.hard[c]);
+            if constexpr (GEO::owns_col(c)) b.lds_write32(B::add(B::shl(lane, 2), B::c(GEO::LDS_HARD + GEO::col_slot(c) * 256)), d.hard[c]);
         });
         sfor<0, NCOLS>([&](auto C_) {
             constexpr int c = decltype(C_)::value;
             if constexpr (GEO::owns_col(c)) {
-                const V out = pack_hard_column<CODE>(b, d, GEO::LDS_HARD + c_slot(c) * 256);
+                const V out = pack_hard_column<CODE>(b, d, GEO::LDS_HARD + GEO::col_slot(c) * 256);
                 b.gstore32(output, B::add(B::mul_u(frame, (uint32_t)GEO::OUT_LEN), B::add(B::c((uint32_t)c * (M / 8)), B::shl(lw, 2))), out, valid);
             }
         });
@@ -227,16 +227,13 @@ struct SplitGroup {
             V iters_v = B::c(iters_s[0]);
             sfor<1, G>([&](auto G_) {
                 constexpr int g = decltype(G_)::value;
-                constexpr uint64_t gm = ((1ull << (W & 63)) - 1) << ((g * W) & 63);
-                iters_v = B::select_lanes(gm, B::c(iters_s[g]), iters_v);
+                iters_v = B::select_lanes(slot_lanes(W, g), B::c(iters_s[g]), iters_v);
             });
             const V first = B::and_(valid, B::eq(lw, B::c(0)));
             b.gstore32(iters, B::shl(frame, 2), iters_v, first);
             b.gstore8(success, frame, B::and_(b.plane_of(ok_mask), B::c(1)), first);
         }
     }
-    // ordinal of block column c among the owned ones (the epilogue's hard-decision words alias the LLR planes)
-    static constexpr int c_slot(int c) { int s = 0; for (int i = 0; i < c; ++i) s += GEO::owns_col(i) ? 1 : 0; return s; }
 
     // ---- slot refill (round 6; decode_refill of decode_ms_bitslice.hpp for a group shared by two waves) --------------------------------
     // A slot whose codeword is finished hands in its results and takes the workgroup's next frame while the other slots iterate.  Both
@@ -261,7 +258,6 @@ struct SplitGroup {
             if (GEO::owns_col(c) && (!tx_only || c < NTX)) lit |= (uint32_t)c << (4 * i++);
         return lit;
     }
-    static constexpr uint64_t all_lanes_of(int) { return W == 64 ? ~0ull : ((1ull << (W & 63)) - 1); }
     V it_v, fr_v;                          // per lane: iterations done by / frame of the lane's slot
     uint64_t rf_active = 0, rf_fin = ~0ull, rf_ok = 0;
     uint32_t rf_next = 0, rf_end = 0;      // the current chunk's next frame without a slot, its end
@@ -347,21 +343,21 @@ struct SplitGroup {
         if (done) {
             sfor<0, NCOLS>([&](auto C_) {
                 constexpr int c = decltype(C_)::value;
-                if constexpr (GEO::owns_col(c)) b.lds_write32(B::add(B::shl(lane, 2), B::c(RF_HARD + c_slot(c) * 256)), d.hard[c]);
+                if constexpr (GEO::owns_col(c)) b.lds_write32(B::add(B::shl(lane, 2), B::c(RF_HARD + GEO::col_slot(c) * 256)), d.hard[c]);
             });
             B::mem_fence();
             while (done) {
                 const int first = __builtin_ctzll(done);                                  // the slot's first lane
                 const uint32_t f = b.readlane(fr_v, first), itv = b.readlane(it_v, first);
                 emit_owned(b, first, output + (size_t)f * GEO::OUT_LEN, iters + f, success + f, itv, (uint32_t)((rf_ok >> first) & 1));
-                done &= ~(all_lanes_of(0) << first);
+                done &= ~(slot_lanes(W, 0) << first);
             }
         }
         rf_active &= ~rf_fin;
         uint64_t vacant = rf_fin, fresh = 0;
         while (vacant && rf_ahead_frame != NO_FRAME) {
             const int first = __builtin_ctzll(vacant);
-            const uint64_t gmask = all_lanes_of(0) << first;
+            const uint64_t gmask = slot_lanes(W, 0) << first;
             const uint32_t f = rf_ahead_frame;
             place_owned(b, first);
             rf_look_ahead(b, draw);

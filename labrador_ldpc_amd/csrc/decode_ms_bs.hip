@@ -27,16 +27,9 @@
 namespace ldpc {
 namespace bs {
 
-// waves per SIMD the kernel is compiled for.  Rate 1/2 (TM2048, TM8192): THREE -- 168 registers -- since round 5: a row's running
-// state replaces its old state with the row's last edge, block row 0 finishes first, the hard decisions live in LDS
-// (decode_ms_bitslice.hpp, "schedule of an iteration").  Rate 2/3: two (256 registers).
-#ifndef BS_WAVES_R12
-#define BS_WAVES_R12 3
-#endif
-template <int CODE> constexpr int waves_per_simd() { return (CODE == TM2048 || CODE == TM8192) ? BS_WAVES_R12 : 2; }
-
+// (waves per SIMD a kernel is compiled for, which unit builds it, whether it has a slot-refill form: BsPlan, decode_ms_bs_plan.hpp)
 template <int CODE>
-__global__ void __launch_bounds__(64, waves_per_simd<CODE>())
+__global__ void __launch_bounds__(64, BsPlan<CODE>::WAVES_PER_SIMD)
 decode_ms_bs_kernel(const int8_t *__restrict__ llrs, uint8_t *__restrict__ output, uint32_t *__restrict__ iters,
                     uint8_t *__restrict__ success, uint32_t batch, uint32_t maxiters, uint32_t ngroups)
 {
@@ -50,7 +43,7 @@ decode_ms_bs_kernel(const int8_t *__restrict__ llrs, uint8_t *__restrict__ outpu
 // (one relaxed atomic per CHUNK frames; the word is zero between launches: every wave draws until its first ticket beyond the last chunk,
 // and the holder of the very last ticket puts the word back).  A finished slot takes the wave's next frame at once.
 template <int CODE>
-__global__ void __launch_bounds__(64, waves_per_simd<CODE>())
+__global__ void __launch_bounds__(64, BsPlan<CODE>::WAVES_PER_SIMD)
 decode_ms_bs_refill_kernel(const int8_t *__restrict__ llrs, uint8_t *__restrict__ output, uint32_t *__restrict__ iters,
                            uint8_t *__restrict__ success, uint32_t batch, uint32_t maxiters, uint32_t *queue, uint32_t chunk)
 {
@@ -90,7 +83,7 @@ __device__ __forceinline__ void split_wave(char *lds, const int8_t *llrs, uint8_
 }
 
 template <int CODE>
-__global__ void __launch_bounds__(128, 2)
+__global__ void __launch_bounds__(128, BsPlan<CODE>::WAVES_PER_SIMD)
 decode_ms_bs_split_kernel(const int8_t *__restrict__ llrs, uint8_t *__restrict__ output, uint32_t *__restrict__ iters, uint8_t *__restrict__ success,
                           uint32_t batch, uint32_t maxiters, uint32_t ngroups)
 {
@@ -130,7 +123,7 @@ __device__ __forceinline__ void split_wave_refill(char *lds, uint32_t *ticket_wo
 }
 
 template <int CODE>
-__global__ void __launch_bounds__(128, 2)
+__global__ void __launch_bounds__(128, BsPlan<CODE>::WAVES_PER_SIMD)
 decode_ms_bs_split_refill_kernel(const int8_t *__restrict__ llrs, uint8_t *__restrict__ output, uint32_t *__restrict__ iters, uint8_t *__restrict__ success,
                                  uint32_t batch, uint32_t maxiters, uint32_t *queue, uint32_t chunk)
 {
@@ -140,125 +133,97 @@ decode_ms_bs_split_refill_kernel(const int8_t *__restrict__ llrs, uint8_t *__res
     else split_wave_refill<CODE, 1>(lds, ticket_word, llrs, output, iters, success, batch, maxiters, queue, chunk);
 }
 
-template <int CODE>
-hipError_t launch_split_refill(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream,
-                               uint32_t *queue)
+// ---- the two launchers, each for the one-wave (BLOCK 64) and the two-wave (BLOCK 128) form of its kernel ----
+// lockstep: one group of G codewords per workgroup, the hardware dispatcher hands them out
+template <auto KERNEL, int BLOCK, int G>
+hipError_t launch_lockstep(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
 {
-    constexpr int G = Geo<CODE>::G;
-    if (batch == 0) return hipSuccess;
-    if (batch > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    const int resident = resident_workgroups<decode_ms_bs_split_refill_kernel<CODE>, 128>();
-    // frames per draw: four rounds of slots, fewer for short launches (at least ~4 draws per resident workgroup)
-    size_t chunk = 4 * (size_t)G;
-    while (chunk > (size_t)G && batch / chunk < 4 * (size_t)resident) chunk /= 2;
-    const size_t nchunks = (batch + chunk - 1) / chunk;
-    const size_t grid = nchunks < (size_t)resident ? nchunks : (size_t)resident;
-    hipLaunchKernelGGL((decode_ms_bs_split_refill_kernel<CODE>), dim3((unsigned)grid), dim3(128), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters,
-                       queue, (uint32_t)chunk);
-    return hipGetLastError();
-}
-
-template <int CODE>
-hipError_t launch_split(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
-{
-    constexpr int G = Geo<CODE>::G;
     if (batch == 0) return hipSuccess;
     if (batch > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const size_t groups = (batch + G - 1) / G;
     const size_t grid = groups < 0x7FFFFFFFull ? groups : 0x7FFFFFFFull;
-    hipLaunchKernelGGL((decode_ms_bs_split_kernel<CODE>), dim3((unsigned)grid), dim3(128), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters,
-                       (uint32_t)groups);
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(BLOCK), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters, (uint32_t)groups);
+    return hipGetLastError();
+}
+
+// slot refill: the resident workgroups draw chunks of frames from the launch's queue word
+template <auto KERNEL, int BLOCK, int G, int ROUNDS>
+hipError_t launch_refill(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream,
+                         uint32_t *queue)
+{
+    if (batch == 0) return hipSuccess;
+    if (batch > 0xFFFFFFF0ull) return hipErrorInvalidValue;
+    const int resident = resident_workgroups<KERNEL, BLOCK>();
+    // frames per draw: ROUNDS rounds of slots, fewer for short launches (at least ~4 draws per resident workgroup)
+    size_t chunk = ROUNDS * (size_t)G;
+    while (chunk > (size_t)G && batch / chunk < 4 * (size_t)resident) chunk /= 2;
+    const size_t nchunks = (batch + chunk - 1) / chunk;
+    const size_t grid = nchunks < (size_t)resident ? nchunks : (size_t)resident;
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(BLOCK), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters, queue, (uint32_t)chunk);
     return hipGetLastError();
 }
 
 uint32_t *bs_queue_word(hipStream_t stream);          // decode_ms_i8.hip: the launch queue's word of (device, stream), or nullptr (claim_counter)
 
+// A code's kernel as its plan says: one wave or two per group; with `refill`, where the build carries the slot-refill form and the
+// stream has a queue word (all but a stream under capture), that form -- 8 rounds of slots per draw, 4 on the two-wave kernel
 template <int CODE>
-hipError_t launch_refill(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream,
-                         uint32_t *queue)
+hipError_t launch_code(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream, int refill)
 {
-    constexpr int G = Geo<CODE>::G;
-    if (batch == 0) return hipSuccess;
-    if (batch > 0xFFFFFFF0ull) return hipErrorInvalidValue;
-    const int resident = resident_workgroups<decode_ms_bs_refill_kernel<CODE>, 64>();
-    // frames per draw: 8 rounds of slots, fewer for short launches (at least ~4 draws per resident wave)
-    size_t chunk = 8 * (size_t)G;
-    while (chunk > (size_t)G && batch / chunk < 4 * (size_t)resident) chunk /= 2;
-    const size_t nchunks = (batch + chunk - 1) / chunk;
-    const size_t grid = nchunks < (size_t)resident ? nchunks : (size_t)resident;
-    hipLaunchKernelGGL((decode_ms_bs_refill_kernel<CODE>), dim3((unsigned)grid), dim3(64), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters,
-                       queue, (uint32_t)chunk);
-    return hipGetLastError();
+    using PLAN = BsPlan<CODE>;
+    constexpr int G = PLAN::G;
+    if constexpr (PLAN::REFILL) {
+        if (uint32_t *queue = refill ? bs_queue_word(stream) : nullptr) {
+            if constexpr (PLAN::TWO_WAVES) return launch_refill<decode_ms_bs_split_refill_kernel<CODE>, 128, G, 4>(llrs, output, iters, success, batch, maxiters, stream, queue);
+            else return launch_refill<decode_ms_bs_refill_kernel<CODE>, 64, G, 8>(llrs, output, iters, success, batch, maxiters, stream, queue);
+        }
+    }
+    if constexpr (PLAN::TWO_WAVES) return launch_lockstep<decode_ms_bs_split_kernel<CODE>, 128, G>(llrs, output, iters, success, batch, maxiters, stream);
+    else return launch_lockstep<decode_ms_bs_kernel<CODE>, 64, G>(llrs, output, iters, success, batch, maxiters, stream);
 }
 
-template <int CODE>
-hipError_t launch(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
+// the codes THIS compile unit builds (BsPlan::UNIT); hipErrorInvalidConfiguration for every other code
+static hipError_t launch_in_unit(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters,
+                          hipStream_t stream, int refill)
 {
-    constexpr int G = Geo<CODE>::G;
-    if (batch == 0) return hipSuccess;
-    if (batch > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const size_t groups = (batch + G - 1) / G;
-    const size_t grid = groups < 0x7FFFFFFFull ? groups : 0x7FFFFFFFull;
-    hipLaunchKernelGGL((decode_ms_bs_kernel<CODE>), dim3((unsigned)grid), dim3(64), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters,
-                       (uint32_t)groups);
-    return hipGetLastError();
+    auto built_here = [&](auto C_) {
+        constexpr int CODE = decltype(C_)::value;
+        if constexpr (BsPlan<CODE>::UNIT == BS_TU) return launch_code<CODE>(llrs, output, iters, success, batch, maxiters, stream, refill);
+        else return hipErrorInvalidConfiguration;
+    };
+    switch (code) {
+        case TM1280: return built_here(IC<TM1280>{});
+        case TM1536: return built_here(IC<TM1536>{});
+        case TM2048: return built_here(IC<TM2048>{});
+        case TM5120: return built_here(IC<TM5120>{});
+        case TM6144: return built_here(IC<TM6144>{});
+        case TM8192: return built_here(IC<TM8192>{});
+        default: return hipErrorInvalidConfiguration;
+    }
 }
 
 }  // namespace bs
 
 // i8 LLRs through the bit-sliced kernel; hipErrorInvalidConfiguration for the codes it is not built for (the TC codes: their
-// circulants are not quarter-wise rotations).  llrs 4-byte aligned, output 4-byte aligned (the caller checks).  Rate 4/5: two waves per group.
-// refill: 1 = slot refill where the code has it (bitslice_refills()), 0 = the lockstep kernels
+// circulants are not quarter-wise rotations).  llrs 4-byte aligned, output 4-byte aligned (the caller checks).
+// refill: 1 = slot refill where the code has it (BsPlan::REFILL), 0 = the lockstep kernels
 hipError_t launch_decode_ms_bitsliced_unit2(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                                             uint32_t maxiters, hipStream_t stream, int refill);
 #if BS_TU == 2
 hipError_t launch_decode_ms_bitsliced_unit2(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                                             uint32_t maxiters, hipStream_t stream, int refill)
 {
-    uint32_t *queue = refill ? bs::bs_queue_word(stream) : nullptr;
-    switch (code) {
-        case TM1280:
-            if (queue) return bs::launch_split_refill<TM1280>(llrs, output, iters, success, batch, maxiters, stream, queue);
-            return bs::launch_split<TM1280>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM1536:
-            if (queue) return bs::launch_refill<TM1536>(llrs, output, iters, success, batch, maxiters, stream, queue);
-            return bs::launch<TM1536>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM5120:
-#ifndef BS_REFILL_TM5120
-#define BS_REFILL_TM5120 0
-#endif
-#if BS_REFILL_TM5120
-            if (queue) return bs::launch_split_refill<TM5120>(llrs, output, iters, success, batch, maxiters, stream, queue);
-#endif
-            return bs::launch_split<TM5120>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM6144: return bs::launch<TM6144>(llrs, output, iters, success, batch, maxiters, stream);
-        default: return hipErrorInvalidConfiguration;
-    }
+    return bs::launch_in_unit(code, llrs, output, iters, success, batch, maxiters, stream, refill);
 }
 #else
 hipError_t launch_decode_ms_bitsliced(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                                       uint32_t maxiters, hipStream_t stream, int refill)
 {
-    // (slot refill on TM2048, G = 4: built, bit-exact, -1 ... -4 %: its codeword passes the staging slab in two pieces -- the "v != 0"
-    // planes of the active slots live behind the hard-decision words -- and four slots lose little to the lockstep:
-    // profiles/r06_kbench/slot_refill_r06.txt.  -DBS_REFILL_R12=1 builds it.)
-#ifndef BS_REFILL_R12
-#define BS_REFILL_R12 0
-#endif
-    switch (code) {
-        case TM2048:
-#if BS_PLANES == 8 && BS_REFILL_R12
-            if (uint32_t *queue = refill ? bs::bs_queue_word(stream) : nullptr)
-                return bs::launch_refill<TM2048>(llrs, output, iters, success, batch, maxiters, stream, queue);
-#endif
-            return bs::launch<TM2048>(llrs, output, iters, success, batch, maxiters, stream);
-        case TM8192: return bs::launch<TM8192>(llrs, output, iters, success, batch, maxiters, stream);
-#if BS_PLANES == 8
-        default: return launch_decode_ms_bitsliced_unit2(code, llrs, output, iters, success, batch, maxiters, stream, refill);
-#else                   // (a 16-plane experiment build, tools/bs_alt_build.sh -DBS_PLANES=16, carries the rate-1/2 codes only)
-        default: return hipErrorInvalidConfiguration;
-#endif
-    }
+    if (!bs::bitsliced_code(code)) return hipErrorInvalidConfiguration;
+    if (bs::BS_DISPATCH[code].unit == BS_TU) return bs::launch_in_unit(code, llrs, output, iters, success, batch, maxiters, stream, refill);
+    // (a 16-plane experiment build, tools/bs_alt_build.sh -DBS_PLANES=16, carries the rate-1/2 codes only)
+    if constexpr (bs::PL != 8) return hipErrorInvalidConfiguration;
+    else return launch_decode_ms_bitsliced_unit2(code, llrs, output, iters, success, batch, maxiters, stream, refill);
 }
 #endif
 

@@ -3,6 +3,7 @@
 // With -DLDPC_SOFT=1 (decode_ms_soft_i8.o): the soft-output forms of the f32-pipe kernels -- the ones the default dispatch takes for
 // small or unaligned batches.  The bit-sliced kernels keep no marginals once a parity vote is taken (decode_ms_bitslice.hpp;
 // DESIGN.md "Soft output"), so `variant` 64 (LABRADOR_LDPC_HIP_VARIANT_BITSLICE) has no soft form.
+#include "decode_ms_bs_plan.hpp"
 #include "decode_ms_launch.hpp"
 
 namespace ldpc {
@@ -11,20 +12,13 @@ constexpr int VARIANT_BITSLICE = 64;
 
 #if !LDPC_SOFT
 // The bit-sliced kernel (decode_ms_bs.hip, decode_ms_bitslice.hpp): `variant` 64, and the DEFAULT for the TM codes from
-// bitslice_min_batch() frames up -- one wave (rate 4/5: two) decodes a group of 64 / (M/32) codewords on its own, so it needs a few
+// BsPlan::MIN_GROUPS groups (decode_ms_bs_plan.hpp) up -- one wave (rate 4/5: two) decodes a group of 64 / (M/32) codewords on its own, so it needs a few
 // thousand groups in flight to fill the chip and takes ~3x as long per codeword as a whole workgroup of the f32-pipe kernels: small
 // batches are faster on those (and a single frame's latency is theirs).  `variant` 1 / 2 / 32 still name the f32-pipe kernels explicitly.
 hipError_t launch_decode_ms_bitsliced(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                                       uint32_t maxiters, hipStream_t stream, int refill);
 // the launch queue's word for the bit-sliced refill kernels (decode_ms_bs.hip does not see decode_ms_launch.hpp)
 namespace bs { uint32_t *bs_queue_word(hipStream_t stream) { return claim_counter(stream); } }
-// groups of 64 / (M/32) codewords from which the bit-sliced kernel is faster per call (tools/bs_crossover.py,
-// profiles/r05_kbench/bs_crossover.txt: TM8192 and TM1280 cross at 1024 groups, TM6144 and TM5120 at 768, TM2048 and TM1536 at 2048)
-constexpr size_t bitslice_min_batch(int code)
-{
-    constexpr size_t groups[NUM_CODES] = {0, 0, 0, 1024, 2048, 2048, 768, 768, 1024};
-    return code >= TM1280 && code <= TM8192 ? groups[code] * (size_t)(64 / (CODES[code].m / 32)) : ~(size_t)0;
-}
 // its loads and stores are dwords: both buffers 4-byte aligned
 static bool bitslice_aligned(const int8_t *llrs, const uint8_t *output) { return (uintptr_t)llrs % 4 == 0 && (uintptr_t)output % 4 == 0; }
 
@@ -43,23 +37,23 @@ static bool pipe_variant_built(int code, int variant)          // an explicit in
 static I8Kernel pick_i8_kernel(int code, int variant, unsigned lflags, size_t batch, bool aligned)
 {
     if (!valid_code(code) || variant < 0) return I8Kernel::NONE;
-    const bool tm = code >= TM1280 && code <= TM8192;
-    const I8Kernel bs = (code == TM1280 || code == TM5120) ? I8Kernel::BITSLICED_SPLIT : I8Kernel::BITSLICED;
-    if (variant == VARIANT_BITSLICE) return tm && aligned ? bs : I8Kernel::NONE;
-    if (variant == 0 && lflags == 0 && batch >= bitslice_min_batch(code) && aligned) return bs;
+    const bs::BsDispatch &plan = bs::BS_DISPATCH[code];             // (a TC code's row: not built, never large enough)
+    const I8Kernel sliced = plan.two_waves ? I8Kernel::BITSLICED_SPLIT : I8Kernel::BITSLICED;
+    if (variant == VARIANT_BITSLICE) return plan.built && aligned ? sliced : I8Kernel::NONE;
+    if (variant == 0 && lflags == 0 && batch >= plan.min_batch && aligned) return sliced;
     if (variant == VARIANT_PAIR) return code == TM8192 ? I8Kernel::PAIR : I8Kernel::NONE;
     if (variant == 0) return code == TM8192 ? I8Kernel::PAIR : I8Kernel::PIPE;
     return pipe_variant_built(code, variant) ? I8Kernel::PIPE : I8Kernel::NONE;
 }
 
-// Slot refill (TM1536, TM1280: a finished codeword's lanes take the next frame at once): by name -- `variant` 64 without STATIC -- at
+// Slot refill (the codes of BsPlan::REFILL -- TM1536, TM1280: a finished codeword's lanes take the next frame at once): by name -- `variant` 64 without STATIC -- at
 // any batch size; in the default dispatch from 4 frames per resident slot up (2 048 waves x 8, 1 024 wave pairs x 16 = 16 384 slots on
 // 256 CUs): with fewer frames per slot there is little to refill with and the per-slot events cost more than the lockstep loses
 // (tools/bs_crossover.py, profiles/r06_kbench/bs_crossover_refill.txt: TM1536 break-even at 65 536 frames, TM1280 between 32 768 and 65 536).
 constexpr size_t REFILL_MIN_BATCH = 65536;
 static bool i8_refills(int code, int variant, unsigned lflags, size_t batch)
 {
-    if ((code != TM1536 && code != TM1280) || (lflags & LF_STATIC)) return false;
+    if (!valid_code(code) || !bs::BS_DISPATCH[code].refill || (lflags & LF_STATIC)) return false;
     return variant == VARIANT_BITSLICE || batch >= REFILL_MIN_BATCH;
 }
 

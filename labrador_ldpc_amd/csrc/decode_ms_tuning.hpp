@@ -1,7 +1,7 @@
 // decode_ms_tuning.hpp -- the tuned settings of the min-sum kernels, in one place.
 //
-// A LIBRARY build uses exactly the values below: a stray -DLDPC_... in the build's flags stops it here instead of shipping a mistuned
-// decoder.  Same-process A/B experiments on these settings, and the timing diagnostics that leave pieces of the decoder out, live
+// A LIBRARY build uses exactly the values below: a stray -DLDPC_... or -DBS_... in the build's flags stops it here instead of shipping a
+// mistuned decoder.  Same-process A/B experiments on these settings, and the timing diagnostics that leave pieces of the decoder out, live
 // outside the library: tools/kbench/ applies its overlay (tools/kbench/diag_overlay.patch) to a COPY of these sources and builds its
 // own binaries from that (tools/kb_build.sh); nothing of it is visible to the library's translation units.
 #pragma once
@@ -12,8 +12,11 @@
     defined(LDPC_PRIO_ROWS_PAIR) || defined(LDPC_SELFCORR_CARRY) || defined(LDPC_WAVE_VERDICT) || defined(LDPC_WG_VERDICT) || \
     defined(LDPC_PEEL_FIRST) || defined(LDPC_SELFCORR_MED3) || defined(LDPC_PAIR_SELFCORR_MED3) || defined(LDPC_LEAN_CH) || \
     defined(LDPC_PAIR_HOIST) || defined(LDPC_PAIR_HOIST_F32) || defined(LDPC_PAIR_EARLY_U) || defined(LDPC_PAIR_EARLY_U_F32) || \
-    defined(LDPC_PAIR_DEFER_LOCAL) || defined(LDPC_PAIR_DEFER_LOCAL_F32) || defined(LDPC_PAIR_LOCAL_IN_VAR_DEFER)
-#error "the LDPC_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/)"
+    defined(LDPC_PAIR_DEFER_LOCAL) || defined(LDPC_PAIR_DEFER_LOCAL_F32) || defined(LDPC_PAIR_LOCAL_IN_VAR_DEFER) || \
+    defined(BS_PLANES) || defined(BS_PIPE) || defined(BS_KEEP_SPLIT) || defined(BS_KEEP_R23) || defined(BS_KEEP_R12) || \
+    defined(BS_PINNED_R12) || defined(BS_PINNED_R23) || defined(BS_PINNED_SPLIT) || defined(BS_HARD_LDS) || defined(BS_NZ_LDS) || defined(BS_WAVES_R12) || \
+    defined(BS_REFILL_TM5120) || defined(BS_REFILL_R12)
+#error "the LDPC_* and BS_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/, tools/bs_alt_build.sh)"
 #endif
 #endif
 
@@ -137,4 +140,58 @@
 // alternatives, also per quarter, measured 6.4-6.75 against 6.75 for this one.
 #ifndef LDPC_PRIO_ROWS_PAIR
 #define LDPC_PRIO_ROWS_PAIR {3, 3, 2, 2, 1, 0}
+#endif
+
+// ---- decode_ms_bitslice.hpp (what an instantiation makes of these, and what each was measured at: BsPlan, decode_ms_bs_plan.hpp;
+// alternative builds beside the library's objects: tools/bs_alt_build.sh, which defines LDPC_TUNING_OVERRIDES_ALLOWED) ----------------
+// Bit planes of a message / marginal (two's complement).  8 = i8, what the library ships.  The kernel text is written for PL planes: a
+// build with -DBS_PLANES=16 decodes with i16 saturation (the experiment behind DESIGN.md section 7: sign-extended i8 LLRs through the
+// i8 loader, checked against the i16 oracle in tests/test_bitslice_emu.py) -- twice the instructions and registers per edge.
+#ifndef BS_PLANES
+#define BS_PLANES 8
+#endif
+// The next permutation job's ds_bpermute issued behind the current job's arithmetic (BsPlan::PIPE), a bit per class of kernel:
+// bit 0 = the two-wave kernels, bit 1 = rate 2/3, bit 2 = rate 1/2.
+#ifndef BS_PIPE
+#define BS_PIPE 3
+#endif
+// Exchanged edges per block column whose (sign, magnitude ^ sign) planes are kept from the variable side for the check side
+// (BsPlan::KEEP), per class of kernel.
+#ifndef BS_KEEP_SPLIT
+#define BS_KEEP_SPLIT 3
+#endif
+#ifndef BS_KEEP_R23
+#define BS_KEEP_R23 3
+#endif
+#ifndef BS_KEEP_R12
+#define BS_KEEP_R12 3
+#endif
+// State updates pinned to their place in the program (BsPlan::PINNED), per class of kernel: 0 / 1.
+#ifndef BS_PINNED_R12
+#define BS_PINNED_R12 0
+#endif
+#ifndef BS_PINNED_R23
+#define BS_PINNED_R23 1
+#endif
+#ifndef BS_PINNED_SPLIT
+#define BS_PINNED_SPLIT 0
+#endif
+// Rate 1/2: hard decisions in LDS instead of one register per block column (BsPlan::HARD_LDS): 0 / 1.
+#ifndef BS_HARD_LDS
+#define BS_HARD_LDS 1
+#endif
+// Rate 1/2: how many edges' "v != 0" planes live in LDS instead of registers (BsPlan::NZ_LDS; none without BS_HARD_LDS).
+#ifndef BS_NZ_LDS
+#define BS_NZ_LDS 4
+#endif
+// Rate 1/2: waves per SIMD the kernels are compiled for (BsPlan::WAVES_PER_SIMD).
+#ifndef BS_WAVES_R12
+#define BS_WAVES_R12 3
+#endif
+// Slot refill for the codes with four slots, built and measured slower (BsPlan::REFILL): 1 = build and dispatch it.
+#ifndef BS_REFILL_TM5120
+#define BS_REFILL_TM5120 0
+#endif
+#ifndef BS_REFILL_R12
+#define BS_REFILL_R12 0
 #endif

@@ -26,7 +26,8 @@ def emu():
     (fully unrolled 64-lane code: ~1 minute each at -O1)."""
     src = [os.path.join(ROOT, "tests", "c", "bitslice_emu.cpp"), os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_bitslice.hpp"),
            os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_bitslice_split.hpp"), os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_bf_bitslice.hpp"),
-           os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "codes.hpp")]
+           os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "codes.hpp"), os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_bs_plan.hpp"),
+           os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_tuning.hpp")]
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     libs, jobs = {}, []
     for name in TM:
@@ -169,9 +170,10 @@ def test_sixteen_plane_build_equals_the_i16_oracle(name):
     code = oracle.CODES.index(name)
     lib = os.path.join(ROOT, "build", f"libbitslice_emu16_{name}.so")
     src = [os.path.join(ROOT, "tests", "c", "bitslice_emu.cpp")] + [os.path.join(ROOT, "labrador_ldpc_amd", "csrc", f) for f in
-           ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "decode_bf_bitslice.hpp", "codes.hpp")]
+           ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "decode_bf_bitslice.hpp", "codes.hpp", "decode_ms_bs_plan.hpp",
+            "decode_ms_tuning.hpp")]
     if not os.path.exists(lib) or any(os.path.getmtime(f) > os.path.getmtime(lib) for f in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", f"-DEMU_CODE={name}", "-DBS_PLANES=16",
+        subprocess.check_call(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", f"-DEMU_CODE={name}", "-DBS_PLANES=16", "-DLDPC_TUNING_OVERRIDES_ALLOWED",
                                "-I" + os.path.join(ROOT, "labrador_ldpc_amd", "csrc"), src[0], "-o", lib])
     L = ctypes.CDLL(lib)
     L.bs_emu_decode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]

@@ -198,3 +198,80 @@ def test_shader_clock_probe_argument_checks_and_no_device_path():
         assert st == -2 and mhz.value == -1.0 and "no HIP device" in la.last_error()
     else:
         assert st == 0 and 1000.0 < mhz.value < 3000.0
+
+
+# labrador_ldpc_hip_decode_ms_i8_kernel over (code, variant, batch): recorded from the library of commit 0f674a5, the last one whose dispatch
+# named its codes by hand (pick_i8_kernel / i8_refills / the launch tables), before they were derived from BsPlan (csrc/decode_ms_bs_plan.hpp).
+# One word per batch of _DISPATCH_BATCHES: "-" = no kernel (the call returns EUNSUPPORTED).
+_DISPATCH_NAMES = {"-": "", "pipe": "decode_ms_kernel", "pair": "decode_ms_pair_kernel", "bs": "decode_ms_bs_kernel", "bs_refill": "decode_ms_bs_refill_kernel",
+                   "split": "decode_ms_bs_split_kernel", "split_refill": "decode_ms_bs_split_refill_kernel"}
+_DISPATCH_MIN_GROUPS = {"TM1280": 1024, "TM1536": 2048, "TM2048": 2048, "TM5120": 768, "TM6144": 768, "TM8192": 1024}
+_DISPATCH_BATCHES = {"TC128": [1], "TC256": [1], "TC512": [1],
+                     "TM1280": [1, 16383, 16384, 16385, 65535, 65536, 65537], "TM1536": [1, 16383, 16384, 16385, 65535, 65536, 65537],
+                     "TM2048": [1, 8191, 8192, 8193, 65535, 65536, 65537], "TM5120": [1, 3071, 3072, 3073, 65535, 65536, 65537],
+                     "TM6144": [1, 1535, 1536, 1537, 65535, 65536, 65537], "TM8192": [1, 1023, 1024, 1025, 65535, 65536, 65537]}
+_DISPATCH_TABLE = {
+    ("TC128", 0): "pipe",
+    ("TC128", 64): "-",
+    ("TC128", 320): "-",
+    ("TC128", 1): "pipe",
+    ("TC128", 32): "-",
+    ("TC256", 0): "pipe",
+    ("TC256", 64): "-",
+    ("TC256", 320): "-",
+    ("TC256", 1): "pipe",
+    ("TC256", 32): "-",
+    ("TC512", 0): "pipe",
+    ("TC512", 64): "-",
+    ("TC512", 320): "-",
+    ("TC512", 1): "pipe",
+    ("TC512", 32): "-",
+    ("TM1280", 0): "pipe pipe split split split split_refill split_refill",
+    ("TM1280", 64): "split_refill split_refill split_refill split_refill split_refill split_refill split_refill",
+    ("TM1280", 320): "split split split split split split split",
+    ("TM1280", 1): "pipe pipe pipe pipe pipe pipe pipe",
+    ("TM1280", 32): "- - - - - - -",
+    ("TM1536", 0): "pipe pipe bs bs bs bs_refill bs_refill",
+    ("TM1536", 64): "bs_refill bs_refill bs_refill bs_refill bs_refill bs_refill bs_refill",
+    ("TM1536", 320): "bs bs bs bs bs bs bs",
+    ("TM1536", 1): "pipe pipe pipe pipe pipe pipe pipe",
+    ("TM1536", 32): "- - - - - - -",
+    ("TM2048", 0): "pipe pipe bs bs bs bs bs",
+    ("TM2048", 64): "bs bs bs bs bs bs bs",
+    ("TM2048", 320): "bs bs bs bs bs bs bs",
+    ("TM2048", 1): "pipe pipe pipe pipe pipe pipe pipe",
+    ("TM2048", 32): "- - - - - - -",
+    ("TM5120", 0): "pipe pipe split split split split split",
+    ("TM5120", 64): "split split split split split split split",
+    ("TM5120", 320): "split split split split split split split",
+    ("TM5120", 1): "pipe pipe pipe pipe pipe pipe pipe",
+    ("TM5120", 32): "- - - - - - -",
+    ("TM6144", 0): "pipe pipe bs bs bs bs bs",
+    ("TM6144", 64): "bs bs bs bs bs bs bs",
+    ("TM6144", 320): "bs bs bs bs bs bs bs",
+    ("TM6144", 1): "pipe pipe pipe pipe pipe pipe pipe",
+    ("TM6144", 32): "- - - - - - -",
+    ("TM8192", 0): "pair pair bs bs bs bs bs",
+    ("TM8192", 64): "bs bs bs bs bs bs bs",
+    ("TM8192", 320): "bs bs bs bs bs bs bs",
+    ("TM8192", 1): "- - - - - - -",
+    ("TM8192", 32): "pair pair pair pair pair pair pair",
+}
+
+
+def test_i8_dispatch_table_is_the_recorded_one():
+    """Which kernel serves an i8 batch is derived from one plan per code (BsPlan); the table it yields must stay the one the hand-written
+    dispatch gave: every code; `variant` 0 (default), 64 (bit-sliced by name), 64|256 (... with a static stride: no slot refill), 1 and 32
+    (f32-pipe kernels by name); one frame, and one frame below, at and one above both thresholds of the TM codes -- MIN_GROUPS groups of
+    64 / (M/32) codewords, where the default turns bit-sliced, and 65 536 frames, where it turns to slot refill.  No GPU needed."""
+    assert sorted(_DISPATCH_BATCHES) == sorted(c.name for c in LDPCCode)
+    assert len(_DISPATCH_TABLE) == 9 * 5
+    for code in LDPCCode:
+        batches = _DISPATCH_BATCHES[code.name]
+        if code.name in _DISPATCH_MIN_GROUPS:                        # (the two thresholds as the issue states them)
+            t = _DISPATCH_MIN_GROUPS[code.name] * 64 // (code.submatrix_size() // 32)
+            assert batches == [1, t - 1, t, t + 1, 65535, 65536, 65537]
+        for variant in (0, 64, 64 | 256, 1, 32):
+            want = [_DISPATCH_NAMES[w] for w in _DISPATCH_TABLE[(code.name, variant)].split()]
+            got = [la.lib.labrador_ldpc_hip_decode_ms_i8_kernel(int(code), variant, b).decode() for b in batches]
+            assert got == want, (code.name, variant, batches, got)

@@ -51,7 +51,8 @@ def test_library_build_refuses_tuning_switches_and_carries_no_diagnostics(tmp_pa
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
     csrc = os.path.join(ROOT, "labrador_ldpc_amd", "csrc")
-    for switch in ("LDPC_PEEL_FIRST=0", "LDPC_WAVE_VERDICT=0", "LDPC_SELFCORR_CARRY=2", "LDPC_PAIR_EARLY_U=0", "LDPC_NOCAP=0", "LDPC_PRIO=0"):
+    for switch in ("LDPC_PEEL_FIRST=0", "LDPC_WAVE_VERDICT=0", "LDPC_SELFCORR_CARRY=2", "LDPC_PAIR_EARLY_U=0", "LDPC_NOCAP=0", "LDPC_PRIO=0",
+                   "BS_PLANES=16", "BS_PIPE=0", "BS_WAVES_R12=2"):
         r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++20", "-fsyntax-only", "-D" + switch, "-I" + csrc,
                             "-x", "hip", os.path.join(csrc, "decode_ms_tuning.hpp")], capture_output=True, text=True)
         assert r.returncode != 0 and "fixed in a library build" in r.stderr, (switch, r.stderr[-300:])

@@ -1,6 +1,6 @@
 """At which batch does the bit-sliced i8 kernel (`variant` 64: one wave per group of codewords, ~2048 groups fill the chip) overtake the
 f32-pipe i8 kernels (a workgroup per codeword group, 256-1024 fill it)?  Time per call of both, batch by batch, same frames --
-the measurement behind bitslice_min_batch() in csrc/decode_ms_i8.hip.     python tools/bs_crossover.py"""
+the measurement behind BsPlan::MIN_GROUPS in csrc/decode_ms_bs_plan.hpp.     python tools/bs_crossover.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,5 +1,6 @@
 """i16 LLRs on TM8192 / TM2048: today's kernel (the f32 pipe) against the 16-plane build of the bit-sliced kernel text
-(tools/bs_alt_build.sh "p16w2:-DBS_PLANES=16 -DBS_WAVES_R12=2": i16 saturation, fed sign-extended i8 LLRs through the i8 loader), same frames.
+(tools/bs_alt_build.sh "p16w2:-DBS_PLANES=16 -DBS_WAVES_R12=2", which builds with LDPC_TUNING_OVERRIDES_ALLOWED -- a library build refuses
+both switches, csrc/decode_ms_tuning.hpp: i16 saturation, fed sign-extended i8 LLRs through the i8 loader), same frames.
     python tools/i16_rate.py                                   -> rates of decode_ms_batch on int16 tensors (default library)
     LABRADOR_LDPC_HIP_LIB=build/alt/liblabrador_ldpc_hip_p16w2.so python tools/i16_rate.py bs16    -> the 16-plane bit-sliced kernel
 Both print a digest of (output, iters, success): the two must agree (the frames' LLRs lie in the i8 range)."""
