@@ -534,6 +534,56 @@ int labrador_ldpc_decode_ms_cascade_corrected_batch_f32(enum labrador_ldpc_code 
                                                         float flooding_offset, float scale, float offset,
                                                         const struct labrador_ldpc_hip_opts *opts);
 
+/* Normalized / offset min-sum on the FLOODING schedule for i8 LLRs, in integers: the flooding decoder of
+ * labrador_ldpc_decode_ms_batch_i8 -- the reference's decode_ms::<i8>, iteration for iteration, with its saturating i8 arithmetic and
+ * |-128| = 127 -- with one step added.  Where an iteration forms an edge's check message, its magnitude m (min2 of the check if |v|
+ * of the edge equals min1, else min1: the previous iteration's minima, 0 <= m <= 127; zero in iteration 0) becomes
+ *     t  = (scale_num * m + ((1 << scale_shift) >> 1)) >> scale_shift     exact; round half up; scale_shift = 0 adds nothing
+ *     m' = max(t - offset, 0)
+ * and the signs are applied to m' as they are to m.  Which of min1 / min2 an edge takes is decided on the uncorrected values;
+ * everything else (self-correction, accumulation order, the stop rule, iters, success, output, max_iters = 0) is the flooding
+ * contract unchanged.  The triple and its ranges are those of labrador_ldpc_decode_ms_layered_fixed_corrected_batch_i8:
+ *   scale_shift  0 .. 8;   scale_num  1 .. 1 << scale_shift (the scale scale_num / 2^scale_shift in (0, 1]);
+ *   offset       0 .. 127, in the UNITS OF THE QUANTISED LLRS.  The TM codes' punctured variables start at 0, and every message into
+ *                them is a minimum over their neighbours' first messages: an offset above those zeroes them for good and no frame
+ *                decodes.  The library chooses no default: DESIGN.md 4.14 gives measured starting points.
+ * A value outside these ranges returns LABRADOR_LDPC_HIP_EINVAL (the message names the parameter).  With scale_num = 1 << scale_shift
+ * and offset = 0 the step is the identity and the results equal those of labrador_ldpc_decode_ms_batch_i8 bit for bit.
+ * A kernel is built per multiplier width: a scale of 1 (the offset alone), a scale with at most four fractional bits (13/16, 3/4,
+ * 7/8 ...), and any other scale.  The first two were measured (the offset alone costs 2 - 4 % of the plain kernel's
+ * rate, a four-bit scale 6 - 26 %); a scale with MORE than four fractional bits selects the widest kernel, whose rate has not been
+ * measured -- it executes about twice the four-bit form's additional instructions.
+ * The kernels are the BIT-SLICED kernels of the six TM codes with the step, at every batch size (no crossover to another kernel
+ * family, the identity triple included): a TC code, and any `variant` but 0, return LABRADOR_LDPC_HIP_EUNSUPPORTED.  Order of the
+ * checks: code, empty batch (OK), NULL buffers, the triple, variant and code family -- all before any device work.  With
+ * LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` must be 4-byte aligned (EINVAL) and `output` 8-byte aligned; the input is always copied in.
+ * Arguments, memory modes, device sets and `stream` as labrador_ldpc_decode_ms_batch_i8.  Hard output only; there is no _multi,
+ * single-frame, i16 or i32 form.  Returns a status code. */
+int labrador_ldpc_decode_ms_corrected_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, uint8_t *output, uint32_t *iters,
+                                               uint8_t *success, size_t batch, size_t max_iters, uint32_t scale_num,
+                                               uint32_t scale_shift, uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+
+/* The i8 cascades with a corrected stage 1: labrador_ldpc_decode_ms_cascade_batch_i8 /
+ * labrador_ldpc_decode_ms_cascade_quantised_batch_i8 whose stage 1 is labrador_ldpc_decode_ms_corrected_batch_i8 at
+ * (flooding_scale_num, flooding_scale_shift, flooding_offset); stage 2 -- the fixed-point layered decoder at (scale_num,
+ * scale_shift, offset) on the original (quantised) LLRs of the frames stage 1 failed -- `stage`, `iters` and everything else are
+ * those calls'.  Both triples are range-checked where those calls check theirs, the stage-1 triple first.  With an identity stage-1
+ * triple (flooding_scale_num = 1 << flooding_scale_shift, flooding_offset = 0) the call IS the plain cascade: any code,
+ * opts->variant included.  With any other stage-1 triple stage 1 is the bit-sliced kernel with the step: a TC code, and any
+ * `variant` but 0, return LABRADOR_LDPC_HIP_EUNSUPPORTED before any device work, and with LABRADOR_LDPC_HIP_MEM_DEVICE the i8 `llrs`
+ * of the first call must be 4-byte aligned.  Returns a status code. */
+int labrador_ldpc_decode_ms_cascade_corrected_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, uint8_t *output, uint32_t *iters,
+                                                       uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters,
+                                                       size_t max_sweeps, uint32_t flooding_scale_num, uint32_t flooding_scale_shift,
+                                                       uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
+                                                       uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8(enum labrador_ldpc_code code, const float *llrs, uint8_t *output,
+                                                                 uint32_t *iters, uint8_t *success, uint8_t *stage, size_t batch,
+                                                                 size_t max_iters, size_t max_sweeps, float scale, int lim,
+                                                                 uint32_t flooding_scale_num, uint32_t flooding_scale_shift,
+                                                                 uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
+                                                                 uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --
  * llrs[i], output[i] (8-byte aligned), iters[i], success[i], laid out as in labrador_ldpc_decode_ms_batch_* -- are DEVICE memory

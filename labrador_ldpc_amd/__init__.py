@@ -99,6 +99,14 @@ SYMBOLS = {
                                                                    _c.c_float, _c.c_float, _optp]),
     **{f"labrador_ldpc_decode_ms_cascade_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32, _c.c_uint32,
                                                              _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    # the bit-sliced i8 flooding kernels with normalized / offset check messages, and the integer cascades with them as stage 1
+    # 
+    "labrador_ldpc_decode_ms_corrected_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]),
+    "labrador_ldpc_decode_ms_cascade_corrected_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32, _c.c_uint32,
+                                                                  _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]),
+    "labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _int,
+                                                                            _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
+                                                                            _c.c_uint32, _optp]),
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -561,11 +569,35 @@ class LDPCCode(enum.IntEnum):
                                                 float(flooding_offset), float(scale), float(offset)),
                                 stage=stage, with_stage=True, types=("f32",))
 
+    def decode_ms_corrected_fixed_batch(self, llrs, scale_num: int, scale_shift: int, offset: int, maxiters: int = 50, output=None,
+                                        iters=None, success=None, stream: Optional[int] = None, devices=None):
+        """Flooding min-sum on int8 LLRs with normalized / offset check messages in integers
+        (labrador_ldpc_decode_ms_corrected_batch_i8): decode_ms_batch on int8 with one step added -- every check
+        message magnitude m becomes max(((scale_num * m + ((1 << scale_shift) >> 1)) >> scale_shift) - offset, 0), the triple as
+        decode_ms_layered_fixed_batch has it.  The bit-sliced kernels of the TM codes at every batch size: a TC code, or any dtype but
+        int8, raises LdpcHipError.  With device buffers `llrs` must be 4-byte aligned.  Buffers, `stream` and `devices` as
+        decode_ms_batch.  Returns (output, iters, success)."""
+        return self._batch_call("labrador_ldpc_decode_ms_corrected_batch_", llrs, maxiters, output, iters, success, 0, stream, devices,
+                                extra=_fixed_correction(scale_num, scale_shift, offset), types=("i8",))
+
     def decode_ms_cascade_fixed_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, output=None, iters=None,
                                       success=None, stage=None, variant: int = 0, stream: Optional[int] = None, devices=None,
-                                      scale_num: Optional[int] = None, scale_shift: Optional[int] = None, offset: Optional[int] = None):
+                                      scale_num: Optional[int] = None, scale_shift: Optional[int] = None, offset: Optional[int] = None,
+                                      flooding_scale_num: Optional[int] = None, flooding_scale_shift: Optional[int] = None,
+                                      flooding_offset: Optional[int] = None):
         """decode_ms_cascade_batch for int8 and int16 LLRs (labrador_ldpc_decode_ms_cascade_batch_i8 / _i16): the second stage is
-        decode_ms_layered_fixed_batch with its `scale_num`, `scale_shift` and `offset` (none given: plain min-sum)."""
+        decode_ms_layered_fixed_batch with its `scale_num`, `scale_shift` and `offset` (none given: plain min-sum).
+
+        `flooding_scale_num`, `flooding_scale_shift`, `flooding_offset`: the first stage as decode_ms_corrected_fixed_batch at that
+        triple (labrador_ldpc_decode_ms_cascade_corrected_batch_i8): int8 LLRs only; with a triple other than an
+        identity, the TM codes and `variant` 0 only.  None given: the plain first stage through the entry point above."""
+        flooding = _fixed_correction(flooding_scale_num, flooding_scale_shift, flooding_offset)
+        if flooding is not None:
+            return self._batch_call("labrador_ldpc_decode_ms_cascade_corrected_batch_", llrs, maxiters, output, iters, success, variant,
+                                    stream, devices,
+                                    extra=(maxiters if max_sweeps is None else max_sweeps, *flooding,
+                                           *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0))), stage=stage, with_stage=True,
+                                    types=("i8",))
         return self._batch_call("labrador_ldpc_decode_ms_cascade_batch_", llrs, maxiters, output, iters, success, variant, stream, devices,
                                 extra=(maxiters if max_sweeps is None else max_sweeps,
                                        *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0))), stage=stage, with_stage=True,
@@ -837,14 +869,14 @@ class LDPCCode(enum.IntEnum):
                                 fn_name="labrador_ldpc_decode_ms_quantised_batch_" + dtype)
 
     def _quantised_call(self, name, llrs, dtype, scale, lim, triple, maxiters, output, iters, success, variant, stream, devices,
-                        caps=(), **kw):
+                        caps=(), flooding=(), **kw):
         """the f32-input calls behind the fixed-point layered decoders and the integer cascade: `dtype` chooses the entry; `caps`
         (the cascade's max_sweeps), the quantiser's pair and the triple (none given: the identity) go behind maxiters"""
         np_dtype = _quantised_dtype(dtype)
         if (_is_torch(llrs) or isinstance(llrs, np.ndarray)) and _suffix_or_none(llrs) != "f32":
             raise ValueError("llrs must be float32")
         lim = int(np.iinfo(np_dtype).max) if lim is None else operator.index(lim)
-        extra = (*caps, float(scale), lim, *(_fixed_correction(*triple) or (1, 0, 0)))
+        extra = (*caps, float(scale), lim, *flooding, *(_fixed_correction(*triple) or (1, 0, 0)))
         return self._batch_call(None, llrs, maxiters, output, iters, success, variant, stream, devices, extra=extra, fn_name=name + dtype,
                                 **kw)
 
@@ -874,13 +906,27 @@ class LDPCCode(enum.IntEnum):
     def decode_ms_cascade_quantised_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, maxiters: int = 50,
                                           max_sweeps: Optional[int] = None, output=None, iters=None, success=None, stage=None,
                                           variant: int = 0, stream: Optional[int] = None, devices=None, scale_num: Optional[int] = None,
-                                          scale_shift: Optional[int] = None, offset: Optional[int] = None):
+                                          scale_shift: Optional[int] = None, offset: Optional[int] = None,
+                                          flooding_scale_num: Optional[int] = None, flooding_scale_shift: Optional[int] = None,
+                                          flooding_offset: Optional[int] = None):
         """Decode float32 `llrs[batch, n]` through the integer cascade of `dtype` ("i8", "i16") in one call
         (labrador_ldpc_decode_ms_cascade_quantised_batch_i8 / _i16): per frame exactly decode_ms_cascade_fixed_batch
         -- flooding at cap `maxiters` and kernel `variant`, then the fixed-point layered decoder at cap `max_sweeps` (None =
         `maxiters`) and the triple on the frames it failed -- on quantise_llrs_batch(llrs, dtype, scale, lim).  With device buffers
         `llrs` must be 16-byte aligned, the call waits on the stream once per chunk of frames, and it must not run on a stream under
-        capture.  Returns (output, iters, success, stage)."""
+        capture.  Returns (output, iters, success, stage).
+
+        `flooding_scale_num`, `flooding_scale_shift`, `flooding_offset`: the first stage's triple, as decode_ms_cascade_fixed_batch
+        has it (labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8): `dtype` "i8" only."""
+        flooding = _fixed_correction(flooding_scale_num, flooding_scale_shift, flooding_offset)
+        if flooding is not None:
+            if dtype != "i8":
+                _quantised_dtype(dtype)
+                raise LdpcHipError(f"no corrected first stage for dtype {dtype} (i8 only)")
+            return self._quantised_call("labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_", llrs, dtype, scale, lim,
+                                        (scale_num, scale_shift, offset), maxiters, output, iters, success, variant, stream, devices,
+                                        caps=(maxiters if max_sweeps is None else max_sweeps,), flooding=flooding, stage=stage,
+                                        with_stage=True)
         return self._quantised_call("labrador_ldpc_decode_ms_cascade_quantised_batch_", llrs, dtype, scale, lim,
                                     (scale_num, scale_shift, offset), maxiters, output, iters, success, variant, stream, devices,
                                     caps=(maxiters if max_sweeps is None else max_sweeps,), stage=stage, with_stage=True)

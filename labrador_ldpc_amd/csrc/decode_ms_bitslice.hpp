@@ -48,11 +48,17 @@
 //    wrapped difference and the overflow flag (Decoder::columns); a row's second edge needs one compare (min2 is still the largest
 //    key); TM1280 rotates lanes with a DPP quad_perm instead of ds_bpermute (BsPlan::QUAD).
 //
+//  * NORMALIZED / OFFSET MIN-SUM (Decoder<..., CORRECTED = true>; the kernels of decode_ms_bs_corrected.hip).  A check
+//    message's magnitude is a multiplexer over the row's two stored minima, so the correction max(((scale_num * m + half) >>
+//    scale_shift) - offset, 0) is applied to those two, once per row and iteration, in bit planes (Decoder::correct_mag) -- never per
+//    edge.  The plain instantiations carry nothing of it.
+//
 // What an instantiation is built with -- the members named above, per code, with what each was measured at -- stands in BsPlan
 // (decode_ms_bs_plan.hpp); the settings behind it (BS_*) in decode_ms_tuning.hpp.
 #pragma once
 
 #include <cstdint>
+#include <type_traits>
 
 #include "codes.hpp"
 #include "decode_ms_bs_plan.hpp"
@@ -391,7 +397,19 @@ struct Arith {
 };
 
 // ---- the decoder of one group of G codewords, executed by one wave --------------------------------------------------------
-template <int CODE, class B, int HALF = -1>
+// The wave-uniform triple of the corrected form; the plain form carries nothing
+struct Correction { uint32_t scale_num = 1, scale_shift = 0, offset = 0; };
+struct NoCorrection {};
+
+// the multiplier bits a corrected form must be built with for (scale_num, scale_shift): 0 = the scale is 1 (the offset alone), else the
+// bits of scale_num << (8 - scale_shift) from its lowest set bit up to bit 7, rounded up to a form that is built (4 or 8)
+constexpr int correction_mulbits(uint32_t scale_num, uint32_t scale_shift)
+{
+    const uint32_t num = scale_num << (8 - scale_shift);
+    return num == 256u ? 0 : (num & 15u) == 0 ? 4 : 8;
+}
+
+template <int CODE, class B, int HALF = -1, bool CORRECTED = false, int MULBITS = 8>
 struct Decoder {
     using V = typename B::V;
     using GEO = Geo<CODE, HALF>;
@@ -409,6 +427,7 @@ struct Decoder {
     V W1[NROWS][PL], W2[NROWS][PL], Sn[NROWS], Pn[NROWS], argn[NROWS][ARG];
     V hard[NCOLS];                      // (unused with Geo::HARD_LDS)
     V fail;                             // OR of the parities of the rows finished in this iteration (decoder.rs:453)
+    [[no_unique_address]] std::conditional_t<CORRECTED, Correction, NoCorrection> corr;      // (read only under CORRECTED)
 
     BS_FN void init_lane(B &b)
     {
@@ -607,6 +626,87 @@ struct Decoder {
         });
     }
 
+    // ---- normalized / offset min-sum: a stored minimum m becomes max(((scale_num * m + half) >> scale_shift) - offset, 0),
+    // half = (1 << scale_shift) >> 1, in bit planes.  The three are wave-uniform scalars.  The shift is brought to 8 first --
+    // (scale_num * m + half) >> scale_shift = (num * m + (half << d)) >> 8 with num = scale_num << d, d = 8 - scale_shift, exactly --
+    // so the quotient is planes 8 .. 14 of one 15-plane sum whatever the shift (at most 255 * 127 + 128 < 1 << 15).
+    // NO BRANCH: a scalar branch inside the iteration makes its body several basic blocks, across which the register allocator spilled
+    // 100 to 250 values (rate 1/2 and the two-wave kernels; docs/experiments.md).  A bit of num is a constant plane instead (all ones or
+    // all zeros, a scalar operand), and what a zero bit would save is saved at compile time: the form is built for MULBITS multiplier
+    // bits -- num's low 8 - MULBITS bits are zero, correction_mulbits() -- and MULBITS = 0 is num = 256, the offset alone.
+    // Shift-and-add from the lowest built bit S0 up: the first partial product is taken as it is; before bit s is added the sum is at
+    // most 127 * ((1 << s) - (1 << S0)) < 1 << (s + 7), so the seven full adders of planes s .. s + 6 end in a carry that IS plane
+    // s + 7 -- no ripple.  The half, 128, rides in bit 7's step, whose plane 7 has no carry in.
+    static BS_FN void correct_mag(V (&m)[MG], uint32_t scale_num, uint32_t scale_shift, uint32_t offset)
+    {
+        static_assert(MG == 7 || !CORRECTED, "the corrected form is built for i8 planes");
+        static_assert(MULBITS == 0 || (MULBITS >= 2 && MULBITS <= 8));
+        if constexpr (MULBITS > 0) {
+            constexpr int ACC = 15, S0 = 8 - MULBITS;
+            const uint32_t num = scale_num << (8 - scale_shift);             // 1 .. 255 here, a multiple of 1 << S0
+            V acc[ACC];
+            sfor<0, ACC>([&](auto K_) { acc[decltype(K_)::value] = B::c(0); });
+            sfor<S0, 8>([&](auto B_) {
+                constexpr int s = decltype(B_)::value;
+                const V bit = B::c(0u - ((num >> s) & 1u));                  // num's bit s as a constant plane
+                if constexpr (s == S0) {
+                    sfor<0, MG>([&](auto K_) { constexpr int k = decltype(K_)::value; acc[s + k] = B::and_(m[k], bit); });
+                } else {
+                    V c;
+                    {
+                        const V x = B::and_(m[0], bit), a = acc[s];
+                        if constexpr (s == 7) {
+                            const V half = B::c(scale_shift != 0 ? 0xFFFFFFFFu : 0u);     // 128, or 0 where nothing is shifted out
+                            acc[s] = op3<TT_XOR3>(a, x, half);
+                            c = op3<TT_MAJ>(a, x, half);
+                        } else {
+                            acc[s] = B::xor_(a, x);
+                            c = B::and_(a, x);
+                        }
+                    }
+                    sfor<1, MG>([&](auto K_) {
+                        constexpr int k = decltype(K_)::value;
+                        const V x = B::and_(m[k], bit), a = acc[s + k];
+                        acc[s + k] = op3<TT_XOR3>(a, x, c);
+                        c = op3<TT_MAJ>(a, x, c);
+                    });
+                    acc[s + MG] = c;
+                }
+                B::fence();                                                  // (bit after bit: the steps are one chain anyway)
+            });
+            sfor<0, MG>([&](auto K_) { constexpr int k = decltype(K_)::value; m[k] = acc[8 + k]; });
+        }
+        // m - offset, clamped at zero by the borrow out
+        V d[MG];
+        V br = B::c(0);
+        sfor<0, MG>([&](auto K_) {
+            constexpr int k = decltype(K_)::value;
+            const V o = B::c(0u - ((offset >> k) & 1u));                     // the offset's bit as a constant plane
+            d[k] = op3<TT_XOR3>(m[k], o, br);
+            br = op3<TT_BORROW>(o, m[k], br);
+        });
+        sfor<0, MG>([&](auto K_) { constexpr int k = decltype(K_)::value; m[k] = B::andn(d[k], br); });
+    }
+    BS_FN void correct_row_minima(V (&ma)[MG], V (&mb)[MG])
+    {
+        B::fence();
+        correct_mag(ma, corr.scale_num, corr.scale_shift, corr.offset);
+        B::fence();                                                          // (one minimum's temporaries at a time)
+        correct_mag(mb, corr.scale_num, corr.scale_shift, corr.offset);
+        B::fence();
+    }
+    // The rows that columns() finishes are corrected together BEHIND the last block column, not inside finish_row(): a row's new old
+    // state is not read before the next iteration, and there the block columns' temporaries are dead.  In split mode that is later
+    // still, in SplitGroup::stage_fetch, when the shared rows' running states are dead as well; a row shared by two waves is
+    // corrected where it is finished (SplitGroup::stage_merge).
+    BS_FN void correct_finished_rows()
+    {
+        sfor<0, NROWS>([&](auto R_) {
+            constexpr int r = decltype(R_)::value;
+            if constexpr (GEO::has_row(r) && !GEO::shared_row(r)) correct_row_minima(m1[r], m2[r]);
+        });
+    }
+
     // ---- a row's running state becomes its old state; minima back to magnitudes: (key + 1) >> 1 = (key >> 1) + (key & 1) ----
     template <int R> BS_FN void finish_row()
     {
@@ -620,6 +720,7 @@ struct Decoder {
         };
         to_mag(W1[R], m1[R]);
         to_mag(W2[R], m2[R]);
+        if constexpr (CORRECTED && GEO::shared_row(R)) correct_row_minima(m1[R], m2[R]);
         S[R] = Sn[R];
         sfor<0, ARG>([&](auto K_) { constexpr int k = decltype(K_)::value; arg[R][k] = argn[R][k]; });
         fail = B::or_(fail, Pn[R]);                                                   // non-zero bits = unsatisfied checks (:453)
@@ -769,6 +870,7 @@ struct Decoder {
                 }
             });
         });
+        if constexpr (CORRECTED && !GEO::SPLIT) correct_finished_rows();
     }
     // ---- split mode: the rows shared with the other wave are finished after their exchange; returns the unsatisfied checks ----
     BS_FN V finish_iteration(B &)
@@ -905,14 +1007,15 @@ BS_FN void init_kernel(B &b)
 // ---- driver: one wave decodes group after group of G codewords ---------------------------------------------------------------
 // llrs [batch][N] i8, output [batch][NP/8] MSB first, iters [batch], success [batch]; `group` = index of the group of G frames.
 // (Lane offsets are relative to the group's first frame, so they fit 32 bits whatever the batch.)
-template <int CODE, class B>
+template <int CODE, class B, bool CORRECTED = false, int MULBITS = 8>
 BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint32_t *iters_all, uint8_t *success_all, uint32_t batch,
-                        uint32_t maxiters, uint32_t group)
+                        uint32_t maxiters, uint32_t group, uint32_t scale_num = 1, uint32_t scale_shift = 0, uint32_t offset = 0)
 {
     using GEO = Geo<CODE>;
     using V = typename B::V;
     constexpr int M = GEO::M, W = GEO::W, G = GEO::G, NTX = GEO::NTX, NCOLS = GEO::NCOLS;
-    Decoder<CODE, B> d;
+    Decoder<CODE, B, -1, CORRECTED, MULBITS> d;
+    if constexpr (CORRECTED) d.corr = Correction{scale_num, scale_shift, offset};
     d.init_lane(b);
     const V lane = d.lane;
     const V cw = B::shr(lane, ilog2c(W));                                    // codeword of the lane inside the group (0 for W = 64)

@@ -40,7 +40,7 @@ struct SplitLayout {
     template <int H> static constexpr int other_x() { return (H == 0 ? XBUF1 : XBUF0) - priv<H>(); }
 };
 
-template <int CODE, class B, int HALF>
+template <int CODE, class B, int HALF, bool CORRECTED = false, int MULBITS = 8>
 struct SplitGroup {
     using V = typename B::V;
     using GEO = Geo<CODE, HALF>;
@@ -51,10 +51,13 @@ struct SplitGroup {
     static constexpr int XO = LAY::template own_x<HALF>(), XT = LAY::template other_x<HALF>();
     template <int TT> static BS_FN V op3(V a, V b, V c) { return B::template bitop3<TT>(a, b, c); }
 
-    Decoder<CODE, B, HALF> d;
+    Decoder<CODE, B, HALF, CORRECTED, MULBITS> d;
     V lane, cw, lw, frame, valid, extra_fail;
     uint64_t valid_mask = 0, frozen_mask = 0, ok_mask = 0;
     uint32_t iters_s[G];                       // verdicts are wave-uniform per codeword: scalars, not planes
+    // the group in hand and the batch, kept by the corrected forms alone, whose epilogue forms `valid` again
+    struct GroupInHand { uint32_t group = 0, batch = 0; };
+    [[no_unique_address]] std::conditional_t<CORRECTED, GroupInHand, NoCorrection> hand;
     const int8_t *llrs = nullptr;
     uint8_t *output = nullptr;
     uint32_t *iters = nullptr;
@@ -62,6 +65,12 @@ struct SplitGroup {
 
     // once per kernel and wave: the lane permutation tables of the owned exchanged edges
     BS_FN void init(B &b) { d.init_lane(b); d.init_perm_tables(b); }
+    // the corrected form's wave-uniform triple, once per kernel and wave
+    BS_FN void set_correction(uint32_t scale_num, uint32_t scale_shift, uint32_t offset)
+    {
+        static_assert(CORRECTED, "the plain form carries no triple");
+        d.corr = Correction{scale_num, scale_shift, offset};
+    }
 
     // ---- LLRs of the owned transmitted columns -> bit planes in LDS; state zeroed ----
     BS_FN void prologue(B &b, const int8_t *llrs_all, uint8_t *output_all, uint32_t *iters_all, uint8_t *success_all, uint32_t batch,
@@ -95,6 +104,7 @@ struct SplitGroup {
         sfor<0, G>([&](auto G_) { iters_s[decltype(G_)::value] = maxiters; });
         ok_mask = 0;
         extra_fail = B::c(0);
+        if constexpr (CORRECTED) hand = GroupInHand{group, batch};
     }
 
     BS_FN bool running() const { return frozen_mask != ~0ull; }
@@ -183,6 +193,8 @@ struct SplitGroup {
     BS_FN void stage_fetch(B &b)
     {
         constexpr int R = PUB;
+        // (the rows only this wave has, Decoder::correct_finished_rows: here, while row PUB's old state is dead -- the fetch replaces it)
+        if constexpr (CORRECTED) d.correct_finished_rows();
         sfor<0, MG>([&](auto K_) {
             constexpr int k = decltype(K_)::value;
             d.m1[R][k] = b.lds_read32(xaddr(lane, XO, k));
@@ -212,6 +224,17 @@ struct SplitGroup {
     // ---- hard decisions of the owned columns, MSB first; iterations and success by wave 0 ----
     BS_FN void epilogue(B &b)
     {
+        // The corrected forms have no register to carry the prologue's lane constants through the iterations (TM5120 spilled ten such
+        // values around its loop): they are formed again here, from an opaque copy of the lane index and the group's scalars, as
+        // decode_group does it.
+        if constexpr (CORRECTED) {
+            d.reinit_lane();
+            lane = d.lane;
+            cw = B::shr(lane, ilog2c(W));
+            lw = B::and_(lane, B::c(W - 1));
+            frame = cw;
+            valid = B::less_u(B::add(B::c(hand.group * (uint32_t)G), cw), B::c(hand.batch));
+        }
         sfor<0, NCOLS>([&](auto C_) {
             constexpr int c = decltype(C_)::value;
             if constexpr (GEO::owns_col(c)) b.lds_write32(B::add(B::shl(lane, 2), B::c(GEO::LDS_HARD + GEO::col_slot(c) * 256)), d.hard[c]);
@@ -456,8 +479,8 @@ struct SplitGroup {
 };
 
 // One wave's program for a group: the HIP kernel calls it with a workgroup barrier for SYNC, every wave of the pair with its HALF.
-template <int CODE, class B, int HALF, class SYNC>
-BS_FN void decode_group_split(B &b, SplitGroup<CODE, B, HALF> &g, const int8_t *llrs, uint8_t *out, uint32_t *iters, uint8_t *ok, uint32_t batch,
+template <int CODE, class B, int HALF, class SYNC, bool CORRECTED = false, int MULBITS = 8>
+BS_FN void decode_group_split(B &b, SplitGroup<CODE, B, HALF, CORRECTED, MULBITS> &g, const int8_t *llrs, uint8_t *out, uint32_t *iters, uint8_t *ok, uint32_t batch,
                               uint32_t maxiters, uint32_t group, SYNC sync)
 {
     g.prologue(b, llrs, out, iters, ok, batch, maxiters, group);

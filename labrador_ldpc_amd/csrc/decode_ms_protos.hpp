@@ -26,6 +26,14 @@ bool decode_ms_reads_llrs_once(int code, int variant);
 
 const char *decode_ms_i8_kernel_name(int code, int variant, size_t batch);      // decode_ms_i8.hip
 
+// The bit-sliced i8 flooding kernels of the TM codes with normalized / offset check messages (decode_ms_bs_corrected.hip, DESIGN.md
+// 4.14): every stored row minimum m becomes max(((scale_num * m + ((1 << scale_shift) >> 1)) >> scale_shift) - offset, 0); the three
+// are the caller's, already range-checked (capi.hip).  The bit-sliced kernel at every batch size, lockstep forms; llrs and output
+// 4-byte aligned (the caller checks).  hipErrorInvalidConfiguration for a TC code.
+hipError_t launch_decode_ms_bitsliced_corrected(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
+                                                uint32_t maxiters, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                hipStream_t stream);
+
 // The flooding schedule on f32 LLRs with normalized / offset check messages (decode_ms_flooding_corrected_f32.hip):
 // the code's default f32 kernel with the correction step; scale and offset are the caller's, already range-checked (capi.hip).
 // app == nullptr launches the hard form.  `variant` 0 only: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).

@@ -26,6 +26,11 @@ bytes costs in BER.  `--flooding-scale` / `--flooding-offset` (`--schedule flood
 decoder -- the whole decode, or the cascade's first stage -- normalized / offset check messages
 (labrador_ldpc_decode_ms_corrected_batch_f32 / labrador_ldpc_decode_ms_cascade_corrected_batch_f32); the offset is in
 the units of the LLRs, as `--offset`; anywhere else they are a ValueError, and the defaults change nothing.
+`--fixed-flooding-scale NUM/DEN` / `--fixed-flooding-offset INT` (`--llr i8` with `--schedule flooding` or `cascade`, `--from-f32`
+included on the cascade) give the i8 flooding decoder -- the whole decode, which without them has no i8 form here, or the cascade's
+first stage -- normalized / offset check messages in integers (labrador_ldpc_decode_ms_corrected_batch_i8 /
+labrador_ldpc_decode_ms_cascade_corrected_batch_i8 / _cascade_quantised_corrected_batch_i8, DESIGN.md 4.14: the bit-sliced kernels of
+the TM codes); NUM/DEN and the offset as `--fixed-scale` / `--fixed-offset`; anywhere else they are a ValueError.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -54,7 +59,8 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
               max_bits: float = 5e7, max_errors: int = 5000, seed: int = 1, device: int = 0, schedule: str = "flooding",
               scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31,
               scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None, from_f32: bool = False,
-              flooding_scale: float = 1.0, flooding_offset: float = 0.0):
+              flooding_scale: float = 1.0, flooding_offset: float = 0.0, flooding_scale_num=None, flooding_scale_shift=None,
+              flooding_fixed_offset=None):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
     min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
@@ -67,7 +73,16 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     decode_ms_cascade_quantised_batch at (`llr_scale`, `llr_lim`).  `llr` "f16" / "bf16": the f32 branch with its frames rounded
     to the format (to nearest, ties to even) and handed to the same methods as half-precision tensors.  `flooding_scale`,
     `flooding_offset`: the FLOODING decoder's normalized / offset min-sum correction (decode_ms_batch's `scale` and `offset`; the
-    flooding schedule and the cascade's first stage, f32 LLRs only; the defaults are plain min-sum)."""
+    flooding schedule and the cascade's first stage, f32 LLRs only; the defaults are plain min-sum).  `flooding_scale_num`,
+    `flooding_scale_shift`, `flooding_fixed_offset`: the i8 flooding decoder's integer correction (decode_ms_corrected_fixed_batch's
+    triple; `llr` "i8" on the flooding schedule -- the only i8 flooding decode here -- and as the cascade's first stage, `from_f32`
+    included there; None, the default, is none)."""
+    fixed_flooding = not (flooding_scale_num is None and flooding_scale_shift is None and flooding_fixed_offset is None)
+    if fixed_flooding and (llr != "i8" or schedule == "layered" or (from_f32 and schedule != "cascade")):
+        raise ValueError("flooding_scale_num, flooding_scale_shift and flooding_fixed_offset belong to i8 LLRs on the flooding schedule "
+                         "and the cascade")
+    if fixed_flooding and schedule == "flooding" and not (scale_num is None and scale_shift is None and fixed_offset is None):
+        raise ValueError("scale_num, scale_shift and fixed_offset belong to the layered schedule and the cascade's second stage")
     if schedule not in ("flooding", "layered", "cascade"):
         raise ValueError(f"unknown schedule {schedule!r}")
     if schedule == "flooding" and (scale != 1.0 or offset != 0.0):
@@ -76,7 +91,7 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         raise ValueError("max_sweeps belongs to the cascade")
     if llr not in FLOAT_LLRS + ("i8", "i16"):
         raise ValueError(f"unknown LLR type {llr!r}")
-    if llr not in FLOAT_LLRS and (schedule == "flooding" or scale != 1.0 or offset != 0.0):
+    if llr not in FLOAT_LLRS and ((schedule == "flooding" and not fixed_flooding) or scale != 1.0 or offset != 0.0):
         raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
     if llr in FLOAT_LLRS and not (scale_num is None and scale_shift is None and fixed_offset is None):
         raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
@@ -85,6 +100,11 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     if (flooding_scale != 1.0 or flooding_offset != 0.0) and (schedule == "layered" or llr != "f32"):
         raise ValueError("flooding_scale and flooding_offset belong to the flooding schedule and the cascade on f32 LLRs")
     import torch
+    from . import _fixed_correction
+    flooding_kw = {}
+    if fixed_flooding:
+        flooding_kw = dict(zip(("flooding_scale_num", "flooding_scale_shift", "flooding_offset"),
+                               _fixed_correction(flooding_scale_num, flooding_scale_shift, flooding_fixed_offset)))
     dev = torch.device("cuda", device)
     k8 = code.k() // 8
     g = torch.Generator(device=dev)
@@ -100,12 +120,15 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)
             decode = code.decode_ms_cascade_quantised_batch if schedule == "cascade" else code.decode_ms_layered_quantised_batch
             out = decode(llrs, llr, llr_scale, llr_lim, maxiters, scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset,
-                         **({"max_sweeps": max_sweeps} if schedule == "cascade" else {}))[0]
+                         **({"max_sweeps": max_sweeps, **flooding_kw} if schedule == "cascade" else {}))[0]
         elif llr not in FLOAT_LLRS:                                          # the same noise, quantised by the i8 channel kernel
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
-            decode = code.decode_ms_cascade_fixed_batch if schedule == "cascade" else code.decode_ms_layered_fixed_batch
-            out = decode(llrs if llr == "i8" else llrs.to(torch.int16), maxiters, scale_num=scale_num, scale_shift=scale_shift,
-                         offset=fixed_offset, **({"max_sweeps": max_sweeps} if schedule == "cascade" else {}))[0]
+            if schedule == "flooding":                                       # (i8 with a flooding triple: checked above)
+                out = code.decode_ms_corrected_fixed_batch(llrs, *flooding_kw.values(), maxiters=maxiters)[0]
+            else:
+                decode = code.decode_ms_cascade_fixed_batch if schedule == "cascade" else code.decode_ms_layered_fixed_batch
+                out = decode(llrs if llr == "i8" else llrs.to(torch.int16), maxiters, scale_num=scale_num, scale_shift=scale_shift,
+                             offset=fixed_offset, **({"max_sweeps": max_sweeps, **flooding_kw} if schedule == "cascade" else {}))[0]
         else:
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)  # :13-18 (frame f <- codeword f)
             if llr != "f32":                                                 # the same frames as the format keeps them
@@ -166,6 +189,10 @@ def main(argv=None):
                     help="fixed-point normalized min-sum factor, DEN a power of two of at most 256 (--llr i8 / i16)")
     ap.add_argument("--fixed-offset", type=int, default=None, metavar="INT",
                     help="fixed-point offset min-sum term in units of the quantiser, >= 0 (--llr i8 / i16)")
+    ap.add_argument("--fixed-flooding-scale", type=fixed_scale, default=None, metavar="NUM/DEN",
+                    help="fixed-point normalized min-sum factor of the i8 flooding decoder (--llr i8, --schedule flooding / cascade)")
+    ap.add_argument("--fixed-flooding-offset", type=int, default=None, metavar="INT",
+                    help="fixed-point offset min-sum term of the i8 flooding decoder, >= 0 (--llr i8, --schedule flooding / cascade)")
     ap.add_argument("--from-f32", action="store_true",
                     help="generate f32 frames and decode them through the f32-input entries (--llr i8 / i16, --schedule layered / cascade)")
     args = ap.parse_args(argv)
@@ -175,13 +202,15 @@ def main(argv=None):
         ap.error("--scale and --offset need --schedule layered")
     if args.schedule != "cascade" and args.max_sweeps is not None:
         ap.error("--max-sweeps needs --schedule cascade")
-    if args.llr not in FLOAT_LLRS and (args.schedule == "flooding" or args.scale != 1.0 or args.offset != 0.0):
+    fixed_flooding = args.fixed_flooding_scale is not None or args.fixed_flooding_offset is not None
+    if args.llr not in FLOAT_LLRS and ((args.schedule == "flooding" and not fixed_flooding) or args.scale != 1.0 or args.offset != 0.0):
         ap.error("--llr i8 / i16 needs --schedule layered without --scale and --offset")
     if args.llr in FLOAT_LLRS and (args.fixed_scale is not None or args.fixed_offset is not None):
         ap.error("--fixed-scale and --fixed-offset need --schedule layered --llr i8 / i16")
     if args.fixed_offset is not None and args.fixed_offset < 0:
         ap.error("--fixed-offset must be >= 0")
     scale_num, scale_shift = args.fixed_scale if args.fixed_scale is not None else (None, None)
+    fl_num, fl_shift = args.fixed_flooding_scale if args.fixed_flooding_scale is not None else (None, None)
     code = LDPCCode[args.code]
     for snr in (float(x) for x in args.snrs.split(",")):
         trials, bits, errors, ber, fe = ms_trials(code, snr, args.noise, args.maxiters, args.batch,
@@ -190,7 +219,8 @@ def main(argv=None):
                                                   llr_scale=args.llr_scale, llr_lim=args.llr_lim, scale_num=scale_num,
                                                   scale_shift=scale_shift, fixed_offset=args.fixed_offset, max_sweeps=args.max_sweeps,
                                                   from_f32=args.from_f32, flooding_scale=args.flooding_scale,
-                                                  flooding_offset=args.flooding_offset)
+                                                  flooding_offset=args.flooding_offset, flooding_scale_num=fl_num,
+                                                  flooding_scale_shift=fl_shift, flooding_fixed_offset=args.fixed_flooding_offset)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 
