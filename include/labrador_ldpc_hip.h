@@ -469,7 +469,7 @@ int labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_i16(enum labrador
  * sends every frame to stage 2 (the layered entry's results, stage all 1); max_sweeps = 0 gives every frame stage 1 failed the
  * layered entry's own answer to max_iters = 0: zero output, iters 0, success 0.  (1, 0) and (1 << k, k, 0) are the identity
  * corrections: plain layered min-sum.  `opts->variant` chooses the stage-1 kernel as in labrador_ldpc_decode_ms_batch_*; stage 2
- * has one kernel.  Hard output only.
+ * has one kernel.  Hard output only; labrador_ldpc_decode_ms_cascade_soft_batch_* below add the marginals.
  * Arguments are checked in this order, all before any device work: `code`; for f32 the range of (scale, offset); an empty batch is
  * OK whatever the pointers; a NULL buffer, `stage` included, is EINVAL; for i8 / i16 the ranges of the triple.  With MEM_DEVICE
  * `output` must be 8-byte aligned; `llrs` need only be aligned to its element (a 16-byte aligned `llrs` is gathered faster).
@@ -583,6 +583,52 @@ int labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8(enum labrador_l
                                                                  uint32_t flooding_scale_num, uint32_t flooding_scale_shift,
                                                                  uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
                                                                  uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+
+/* The cascade with SOFT OUTPUT: labrador_ldpc_decode_ms_cascade_batch_<T> that also returns every frame's
+ * a-posteriori LLRs.  Per frame f, exactly, the two separate soft calls composed:
+ *     (a1, o1, i1, s1) = labrador_ldpc_decode_ms_soft_batch_<T> on frame f at cap max_iters, kernel opts->variant
+ *                        (f32 with a stage-1 pair other than (1, 0): labrador_ldpc_decode_ms_corrected_soft_batch_f32 at
+ *                        (flooding_scale, flooding_offset))
+ *     if s1:  app, output, iters, success, stage = a1, o1, i1, 1, 0
+ *     else:   (a2, o2, i2, s2) = f32:      labrador_ldpc_decode_ms_layered_corrected_soft_batch_f32 at (scale, offset)
+ *                                i8 / i16: labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_<T> at (scale_num, scale_shift, offset)
+ *                                on the ORIGINAL LLRs of frame f at cap max_sweeps, variant 0
+ *             app, output, iters, success, stage = a2, o2, i2, s2, 1
+ * output, iters, success and stage equal, bit for bit, what the hard cascade entry of the same type and arguments returns (for f32,
+ * labrador_ldpc_decode_ms_cascade_corrected_batch_f32: the one soft entry carries both pairs, and at the identity stage-1 pair it is
+ * the plain cascade made soft).
+ *   app  [batch][n + p]   punctured variables last, as for the other soft entries.
+ *        f32: float.  The +-0 and NaN rules are those of the stage the frame carries (labrador_ldpc_decode_ms_soft_batch_f32,
+ *             labrador_ldpc_decode_ms_layered_soft_batch_f32).
+ *        i8 / i16: int32_t, the marginal type of the fixed-point layered decoder.  A stage-0 frame holds the flooding decoder's
+ *             SATURATING marginal of the LLR type, sign-extended (-128 .. 127, -32768 .. 32767); a stage-1 frame holds the layered
+ *             decoder's EXACT int32 sum, which may lie far outside that range.  `stage` says which: two frames' marginals are
+ *             comparable only within a stage.
+ * max_iters = 0: stage 1 fails every frame with zero marginals, and every frame goes to stage 2 (stage all 1, app the layered
+ * decoder's).  max_sweeps = 0: the frames stage 1 failed carry what the layered soft entry returns at cap 0.
+ * The integer entries have no stage-1 correction: the corrected bit-sliced kernels have no soft form.  Nor have the plain bit-sliced
+ * kernels, so soft i8 on the TM codes runs the f32-pipe i8 kernel, as labrador_ldpc_decode_ms_soft_batch_i8 does: THE FIRST STAGE OF
+ * THE i8 SOFT CASCADE ON A TM CODE THEREFORE RUNS AT THE f32-PIPE RATE, not at the bit-sliced rate of the hard cascade (DESIGN.md 4.4,
+ * 4.15).  `variant` 64 (the bit-sliced kernels) returns LABRADOR_LDPC_HIP_EUNSUPPORTED with the soft flooding entry's text.
+ * Checks, in the hard cascade's order and with its texts: `code`; for f32 both pairs, before the batch is looked at; an empty batch
+ * is OK and touches nothing; a NULL buffer, `app` and `stage` included, is EINVAL; for i8 / i16 the triple; f32 with a stage-1 pair
+ * other than (1, 0) and `variant` != 0 is EUNSUPPORTED -- all before any device work.  With MEM_DEVICE `output` must be 8-byte and
+ * `app` 16-byte aligned (EINVAL).  Synchronisation of opts->stream, host buffers, device sets and everything else as
+ * labrador_ldpc_decode_ms_cascade_batch_*; LABRADOR_LDPC_HIP_CASCADE_CHUNK also bounds the chunks of frames in which the integer
+ * entries run stage 1 (its marginals pass through a bounded workspace on their way to int32).  There is no quantised (f32-in), f16 /
+ * bf16 or _multi form.  Returns a status code. */
+int labrador_ldpc_decode_ms_cascade_soft_batch_f32(enum labrador_ldpc_code code, const float *llrs, float *app, uint8_t *output,
+                                                   uint32_t *iters, uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters,
+                                                   size_t max_sweeps, float flooding_scale, float flooding_offset, float scale,
+                                                   float offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_soft_batch_i8 (enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app, uint8_t *output,
+                                                   uint32_t *iters, uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters,
+                                                   size_t max_sweeps, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                   const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_soft_batch_i16(enum labrador_ldpc_code code, const int16_t *llrs, int32_t *app, uint8_t *output,
+                                                   uint32_t *iters, uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters,
+                                                   size_t max_sweeps, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                   const struct labrador_ldpc_hip_opts *opts);
 
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --

@@ -99,6 +99,11 @@ SYMBOLS = {
                                                                    _c.c_float, _c.c_float, _optp]),
     **{f"labrador_ldpc_decode_ms_cascade_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32, _c.c_uint32,
                                                              _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    # the cascade with soft output: `app` behind llrs; the f32 entry carries both pairs
+    "labrador_ldpc_decode_ms_cascade_soft_batch_f32": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _c.c_float,
+                                                              _c.c_float, _c.c_float, _optp]),
+    **{f"labrador_ldpc_decode_ms_cascade_soft_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32,
+                                                                  _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
     # the bit-sliced i8 flooding kernels with normalized / offset check messages, and the integer cascades with them as stage 1
     # 
     "labrador_ldpc_decode_ms_corrected_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]),
@@ -602,6 +607,35 @@ class LDPCCode(enum.IntEnum):
                                 extra=(maxiters if max_sweeps is None else max_sweeps,
                                        *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0))), stage=stage, with_stage=True,
                                 types=("i8", "i16"))
+
+    def decode_ms_cascade_soft_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, app=None, output=None, iters=None,
+                                     success=None, stage=None, variant: int = 0, stream: Optional[int] = None, devices=None,
+                                     scale: float = 1.0, offset: float = 0.0, flooding_scale: float = 1.0, flooding_offset: float = 0.0):
+        """decode_ms_cascade_batch with soft output (labrador_ldpc_decode_ms_cascade_soft_batch_f32): also every
+        frame's marginals from the stage it carries -- per frame exactly decode_ms_soft_batch at (`flooding_scale`,
+        `flooding_offset`), and for the frames it failed decode_ms_layered_soft_batch at (`scale`, `offset`).  float32 LLRs only.
+        Buffers, `stream` and `devices` as decode_ms_cascade_batch.  Returns (app[batch, n + p] float32 -- punctured variables
+        last --, output, iters, success, stage); the last four are what decode_ms_cascade_batch returns."""
+        return self._batch_call("labrador_ldpc_decode_ms_cascade_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices, soft=True, app=app,
+                                extra=(maxiters if max_sweeps is None else max_sweeps, float(flooding_scale), float(flooding_offset),
+                                       float(scale), float(offset)),
+                                stage=stage, with_stage=True, types=("f32",))
+
+    def decode_ms_cascade_fixed_soft_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, app=None, output=None,
+                                           iters=None, success=None, stage=None, variant: int = 0, stream: Optional[int] = None,
+                                           devices=None, scale_num: Optional[int] = None, scale_shift: Optional[int] = None,
+                                           offset: Optional[int] = None):
+        """decode_ms_cascade_fixed_batch with soft output, for int8 and int16 LLRs (labrador_ldpc_decode_ms_cascade_soft_batch_i8 /
+        _i16).  `app` is ALWAYS int32: a stage-0 frame holds the flooding decoder's saturating marginal of the LLR
+        type, sign-extended; a stage-1 frame the layered decoder's exact sum -- marginals are comparable only within a stage.  There
+        is no first-stage triple, and on a TM code the int8 first stage is the soft flooding kernel, not the bit-sliced one.
+        Returns (app[batch, n + p] int32, output, iters, success, stage)."""
+        return self._batch_call("labrador_ldpc_decode_ms_cascade_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
+                                devices, soft=True, app=app, app_dtype="i32",
+                                extra=(maxiters if max_sweeps is None else max_sweeps,
+                                       *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0))),
+                                stage=stage, with_stage=True, types=("i8", "i16"))
 
     def _batch_call(self, prefix, llrs, maxiters, output, iters, success, variant, stream, devices, soft=False, app=None, extra=(),
                     app_dtype=None, with_stage=False, stage=None, types=None, fn_name=None, half=False):

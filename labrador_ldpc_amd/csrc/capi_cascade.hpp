@@ -20,7 +20,8 @@ size_t workspace_chunk_frames(size_t llr_row_bytes, const char *env_name)
 size_t cascade_chunk_frames(size_t llr_row_bytes) { return workspace_chunk_frames(llr_row_bytes, "LABRADOR_LDPC_HIP_CASCADE_CHUNK"); }
 
 // Device memory between the two stages, grow-only, per calling thread and per device like StagingPool: `index` holds the counter
-// and the list of failed frames of a slice, `data` a chunk's gathered LLRs and dense stage-2 results.  Calls of one thread may use
+// and the list of failed frames of a slice, `data` a chunk's gathered LLRs and dense stage-2 results (and, before them, a chunk of
+// the integer soft cascade's stage-1 marginals).  Calls of one thread may use
 // different streams: `last_use` is recorded on a call's stream behind its last use of the workspace, and the next call makes its
 // own stream wait for it before it touches the workspace.  The count comes back through a pinned word, read after the call's own
 // synchronisation, so it needs no such care.  The fused quantise-and-decode (capi_quantise.hpp) keeps a second one of these for its
@@ -80,25 +81,62 @@ struct CascadeWorkspace {
     struct Use {
         CascadeWorkspace &ws;
         hipStream_t stream;
+        Use(CascadeWorkspace &w, hipStream_t s) : ws(w), stream(s) {}
+        Use(const Use &) = delete;
         ~Use() { if (hipEventRecord(ws.last_use, stream) == hipSuccess) ws.pending = true; else (void)hipGetLastError(); }
     };
 };
 thread_local CascadeWorkspace g_cascade;
 
 // One launch slice of the cascade: stage 1 on every frame, the list of the frames it failed, their count read back (the one
-// synchronisation of `stream`), then gather, stage 2 and scatter in chunks of the failed frames.  stage1(llrs, output, iters,
-// success, frames, stream) and stage2(dense llrs, dense output, dense iters, dense success, frames, stream) enqueue the two decoders.
-template <class T, class Stage1, class Stage2>
+// synchronisation of `stream`), then gather, stage 2 and scatter in chunks of the failed frames.  stage1(llrs, app of T or NULL,
+// output, iters, success, frames, stream) and stage2(dense llrs, dense app of A or NULL, dense output, dense iters, dense success,
+// frames, stream) enqueue the two decoders.
+// With `app` (the soft cascade; A = T for float, int32 for the integers) every frame's marginals go to its row of
+// [nb][n + p]: stage 2 writes dense rows into the workspace, scattered like the rest.  Stage 1 of float writes the caller's rows
+// themselves -- a frame that stage 2 takes is overwritten.  Stage 1 of the integers stores marginals of T: it runs in chunks of
+// frames, back to back on the stream, each into the workspace's `data` block and widened from there into the caller's int32 rows
+// (never in place: a parallel front-to-back widening overwrites sources not yet read); the workspace is therefore taken before
+// stage 1 then, and `compact` still runs once, over the whole slice.
+template <class T, class A = T, class Stage1, class Stage2>
 hipError_t cascade_slice(const ldpc::CodeInfo &ci, const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
-                         size_t nb, hipStream_t stream, const Stage1 &stage1, const Stage2 &stage2)
+                         size_t nb, hipStream_t stream, const Stage1 &stage1, const Stage2 &stage2, A *app = nullptr)
 {
-    if (hipError_t e = stage1(llrs, output, iters, success, nb, stream); e != hipSuccess) return e;
+    constexpr bool WIDENS = !std::is_same_v<T, A>;
+    const size_t n = ci.n, np = (size_t)ci.n + ci.p, out_len = ci.output_len();
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     CascadeWorkspace &ws = g_cascade;
-    if (hipError_t e = ws.ensure(); e != hipSuccess) return e;
     constexpr size_t LIST_AT = 16;                                  // the counter's word, then the list
-    if (hipError_t e = ws.reserve(ws.index, LIST_AT + nb * sizeof(uint32_t)); e != hipSuccess) return e;
-    if (hipError_t e = ws.wait_for_last_use(stream); e != hipSuccess) return e;
-    CascadeWorkspace::Use use{ws, stream};
+    std::optional<CascadeWorkspace::Use> use;
+    auto take_workspace = [&]() -> hipError_t {
+        if (hipError_t e = ws.ensure(); e != hipSuccess) return e;
+        if (hipError_t e = ws.reserve(ws.index, LIST_AT + nb * sizeof(uint32_t)); e != hipSuccess) return e;
+        if (hipError_t e = ws.wait_for_last_use(stream); e != hipSuccess) return e;
+        use.emplace(ws, stream);
+        return hipSuccess;
+    };
+    bool stage1_done = false;
+    if constexpr (WIDENS) {
+        if (app) {
+            if (hipError_t e = take_workspace(); e != hipSuccess) return e;
+            const size_t chunk = std::min(cascade_chunk_frames(np * sizeof(T)), nb);
+            if (hipError_t e = ws.reserve(ws.data, up(chunk * np * sizeof(T))); e != hipSuccess) return e;
+            T *const d_app = static_cast<T *>(ws.data.p);
+            for (size_t f0 = 0; f0 < nb; f0 += chunk) {
+                const size_t nf = std::min(chunk, nb - f0);
+                if (hipError_t e = stage1(llrs + f0 * n, d_app, output + f0 * out_len, iters + f0, success + f0, nf, stream); e != hipSuccess)
+                    return e;
+                if (hipError_t e = ldpc::launch_cascade_widen_app<T>(d_app, app + f0 * np, nf * np, stream); e != hipSuccess) return e;
+            }
+            stage1_done = true;
+        }
+    }
+    if (!stage1_done) {
+        T *app1 = nullptr;
+        if constexpr (!WIDENS) app1 = app;
+        if (hipError_t e = stage1(llrs, app1, output, iters, success, nb, stream); e != hipSuccess) return e;
+        if (hipError_t e = take_workspace(); e != hipSuccess) return e;
+    }
 
     uint32_t *const count = static_cast<uint32_t *>(ws.index.p);
     uint32_t *const list = reinterpret_cast<uint32_t *>(static_cast<char *>(ws.index.p) + LIST_AT);
@@ -109,22 +147,25 @@ hipError_t cascade_slice(const ldpc::CodeInfo &ci, const T *llrs, uint8_t *outpu
     if (failed == 0) return hipSuccess;
     if (failed > nb) return hipErrorUnknown;
 
-    const size_t n = ci.n, out_len = ci.output_len();
-    const size_t chunk = std::min(cascade_chunk_frames(n * sizeof(T)), failed);
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    // (a chunk's LLR rows fit 256 MiB, and with marginals its rows of them, the longer ones, do)
+    const size_t chunk = std::min(cascade_chunk_frames(app ? np * sizeof(A) : n * sizeof(T)), failed);
     const size_t at_out = up(chunk * n * sizeof(T)), at_iters = at_out + up(chunk * out_len), at_ok = at_iters + up(chunk * sizeof(uint32_t));
-    if (hipError_t e = ws.reserve(ws.data, at_ok + up(chunk)); e != hipSuccess) return e;
+    const size_t at_app = at_ok + up(chunk);
+    if (hipError_t e = ws.reserve(ws.data, at_app + (app ? up(chunk * np * sizeof(A)) : 0)); e != hipSuccess) return e;
     char *const base = static_cast<char *>(ws.data.p);
     T *const d_llrs = reinterpret_cast<T *>(base);
     uint8_t *const d_out = reinterpret_cast<uint8_t *>(base + at_out), *const d_ok = reinterpret_cast<uint8_t *>(base + at_ok);
     uint32_t *const d_iters = reinterpret_cast<uint32_t *>(base + at_iters);
+    A *const d_app = app ? reinterpret_cast<A *>(base + at_app) : nullptr;
     for (size_t c0 = 0; c0 < failed; c0 += chunk) {
         const size_t nc = std::min(chunk, failed - c0);
         if (hipError_t e = ldpc::launch_cascade_gather<T>(llrs, n, list + c0, nc, d_llrs, stream); e != hipSuccess) return e;
-        if (hipError_t e = stage2(d_llrs, d_out, d_iters, d_ok, nc, stream); e != hipSuccess) return e;
+        if (hipError_t e = stage2(d_llrs, d_app, d_out, d_iters, d_ok, nc, stream); e != hipSuccess) return e;
         if (hipError_t e = ldpc::launch_cascade_scatter(list + c0, nc, d_out, d_iters, d_ok, out_len, output, iters, success, stage, stream);
             e != hipSuccess)
             return e;
+        if (app)
+            if (hipError_t e = ldpc::launch_cascade_scatter_rows(list + c0, nc, d_app, np * sizeof(A), app, stream); e != hipSuccess) return e;
     }
     return hipSuccess;
 }

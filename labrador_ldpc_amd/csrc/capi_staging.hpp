@@ -9,7 +9,7 @@ namespace {
 // hipMalloc/hipFree pair per frame (they are freed when the thread exits).
 struct StagingPool {
     struct Slot { void *p = nullptr; size_t cap = 0; int dev = -1; };
-    Slot slots[10];
+    Slot slots[12];
     ~StagingPool() { for (auto &s : slots) if (s.p) (void)hipFree(s.p); }
     hipError_t get(int idx, size_t bytes, void **out)
     {
@@ -178,7 +178,7 @@ template <int NOUT, class Launch>
 int host_pipeline(const void *in, size_t in_bytes_per_item, const HostOut *outs, size_t items,
                   hipStream_t user_stream, Launch launch, bool direct_in = false)
 {
-    static_assert(NOUT >= 1 && NOUT <= 4, "two staging sets of 1 + NOUT buffers share the 10 pool slots");
+    static_assert(NOUT >= 1 && NOUT <= 5, "two staging sets of 1 + NOUT buffers share the 12 pool slots");
     constexpr int SET_SLOTS = NOUT <= 3 ? 4 : 1 + NOUT;        // pool slots per staging set
     // No stream given (the reference-shaped single-frame entries, every host-buffer call with opts == NULL): the calling THREAD's own
     // non-blocking stream, not the legacy null stream -- N host threads looping single-frame decodes (the unchanged-perftest shape,

@@ -1,4 +1,5 @@
-// cascade.hpp -- the three streaming kernels between the two stages of the cascade decode (see cascade.hip).
+// cascade.hpp -- the streaming kernels between the two stages of the cascade decode (see cascade.hip), and the two
+// more that the soft cascade moves its marginals with (cascade_app.hip).
 // Declarations only: capi.hip calls them and does not see the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,4 +19,14 @@ hipError_t launch_cascade_gather(const T *llrs, size_t n, const uint32_t *list, 
 hipError_t launch_cascade_scatter(const uint32_t *list, size_t listed, const uint8_t *d_output, const uint32_t *d_iters,
                                   const uint8_t *d_success, size_t output_len, uint8_t *output, uint32_t *iters, uint8_t *success,
                                   uint8_t *stage, hipStream_t stream);
+// dest row list[i] = dense row i, rows of row_bytes (the dense marginals of stage 2 back to the frames' rows).  Both bases are
+// 16-byte aligned and row_bytes is a multiple of 16 -- every code's (n + p) * 4 is (asserted in cascade_app.hip);
+// listed * row_bytes / 16 < 2^32.  Anything else is hipErrorInvalidValue.
+hipError_t launch_cascade_scatter_rows(const uint32_t *list, size_t listed, const void *dense, size_t row_bytes, void *dest,
+                                       hipStream_t stream);
+// dst [elems] = src [elems] sign-extended, T = int8_t / int16_t (stage 1's marginals of the LLR type into int32 rows).  Both bases
+// are 16-byte aligned, elems is a multiple of 4 and may be any size_t: the launcher loops over launches of 2^30 workgroups.  The
+// two ranges do not overlap.
+template <class T>
+hipError_t launch_cascade_widen_app(const T *src, int32_t *dst, size_t elems, hipStream_t stream);
 }

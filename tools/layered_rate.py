@@ -16,6 +16,11 @@ Decoders (default: all):
                                                           layered decoder (plain; i8 at (13, 4, 0)) on the frames it failed, cap 25 each
     cascade_f32_fc                                        labrador_ldpc_decode_ms_cascade_corrected_batch_f32: cascade_f32 with its first
                                                           stage at (0.8125, 0)
+    cascade_i16                                           labrador_ldpc_decode_ms_cascade_batch_i16, plain second stage
+    cascade_soft_f32, cascade_soft_i8, cascade_soft_i16   labrador_ldpc_decode_ms_cascade_soft_batch_* (DESIGN.md 4.15): the cascade of the type
+                                                          with every frame's marginals, both stages plain
+    soft_flooding_f32, soft_flooding_i8, soft_flooding_i16  labrador_ldpc_decode_ms_soft_batch_*: the first of the two soft calls a caller
+                                                          composes without the soft cascade (the second runs on the failed frames only)
 The f32 frames are awgn_frames(dtype="f32"); the i8 frames are the i8 channel kernel's quantisation (8 / 31) of the same job seed, and
 the i16 frames are those widened.  Passes: a flooding decode that succeeds at iteration index i made i passes, a layered one at sweep
 index i made i + 1; a failure counts as 25.  Cases: TC512 3 dB, TM2048 1.7 and 2 dB, TM8192 2 dB.  Default 1 048 576
@@ -27,7 +32,9 @@ same for fixed_i8_16_4_0 against fixed_i8), every decoder's rate `_over_layered_
 counterpart's, and every corrected fixed decoder's `_over_fixed_i8`.  A cascade decoder also reports `stage2_share`, the share of frames its
 first stage failed, counts a frame's passes as its flooding iterations plus, for those, 25 and its sweeps, and has its rate over its
 flooding counterpart's and over its layered counterpart's (`CASCADE`).  The corrected flooding decoders have their rate
-`_over_flooding_f32`, the plain kernel of the same run, and cascade_f32_fc also `_over_cascade_f32`."""
+`_over_flooding_f32`, the plain kernel of the same run, and cascade_f32_fc also `_over_cascade_f32`.  A soft cascade has its rate over
+the hard cascade of its type and over the soft flooding decoder of its type, and `hard_equals_cascade`: its output, iters, success and
+stage equal the hard cascade's."""
 import argparse
 import ctypes
 import json
@@ -50,9 +57,17 @@ FLOODING_CORRECTED = {"flooding_f32_13_16": (0.8125, 0.0), "flooding_f32_o0.1": 
 DECODERS = {"flooding_f32": ("f32", None), **{k: ("f32", None) for k in FLOODING_CORRECTED}, "layered_f32": ("f32", "flooding_f32"), **{k: ("f32", "flooding_f32") for k in CORRECTED},
             "flooding_i8": ("i8", None), "fixed_i8": ("i8", "flooding_i8"), "fixed_i16": ("i16", "flooding_i8"),
             **{k: ("i8", "flooding_i8") for k in FIXED_CORRECTED},
-            "cascade_f32": ("f32", "flooding_f32"), "cascade_f32_fc": ("f32", "flooding_f32"), "cascade_i8": ("i8", "flooding_i8"), "cascade_i8_13_4_0": ("i8", "flooding_i8")}
+            "cascade_f32": ("f32", "flooding_f32"), "cascade_f32_fc": ("f32", "flooding_f32"), "cascade_i8": ("i8", "flooding_i8"), "cascade_i8_13_4_0": ("i8", "flooding_i8"),
+            "cascade_i16": ("i16", "flooding_i8"), "cascade_soft_f32": ("f32", "flooding_f32"), "cascade_soft_i8": ("i8", "flooding_i8"),
+            "cascade_soft_i16": ("i16", "flooding_i8"),
+            "soft_flooding_f32": ("f32", None), "soft_flooding_i8": ("i8", None), "soft_flooding_i16": ("i16", None)}
 # cascade decoder -> (its layered counterpart, the fixed-point correction of its second stage)
-CASCADE = {"cascade_f32": ("layered_f32", None), "cascade_f32_fc": ("layered_f32", None), "cascade_i8": ("fixed_i8", None), "cascade_i8_13_4_0": ("fixed_i8_13_4_0", (13, 4, 0))}
+CASCADE = {"cascade_f32": ("layered_f32", None), "cascade_f32_fc": ("layered_f32", None), "cascade_i8": ("fixed_i8", None), "cascade_i8_13_4_0": ("fixed_i8_13_4_0", (13, 4, 0)),
+           "cascade_i16": ("fixed_i16", None), "cascade_soft_f32": ("layered_f32", None), "cascade_soft_i8": ("fixed_i8", None),
+           "cascade_soft_i16": ("fixed_i16", None)}
+# soft cascade -> (the hard cascade of its type, the soft flooding decoder of its type)
+CASCADE_SOFT = {f"cascade_soft_{t}": (f"cascade_{t}", f"soft_flooding_{t}") for t in ("f32", "i8", "i16")}
+SOFT_FLOODING = tuple(v[1] for v in CASCADE_SOFT.values())
 
 
 def corrected_call(code, llrs, out, it, ok, scale, offset):
@@ -97,6 +112,9 @@ def main():
         it = {k: torch.empty(frames, dtype=torch.int32, device=dev) for k in keys}
         ok = {k: torch.empty(frames, dtype=torch.uint8, device=dev) for k in keys}
         stage = {k: torch.empty(frames, dtype=torch.uint8, device=dev) for k in keys if k in CASCADE}
+        np_len = code.n() + code.punctured_bits()
+        app = {k: torch.empty((frames, np_len), dtype=torch.int32 if k in CASCADE_SOFT and k != "cascade_soft_f32" else llrs[DECODERS[k][0]].dtype,
+                              device=dev) for k in keys if k in CASCADE_SOFT or k in SOFT_FLOODING}
 
         def call(k):
             x = llrs[DECODERS[k][0]]
@@ -109,6 +127,11 @@ def main():
                 num, shift, offset = FIXED_CORRECTED[k]
                 return lambda: code.decode_ms_layered_fixed_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], scale_num=num,
                                                                   scale_shift=shift, offset=offset)
+            if k in SOFT_FLOODING:
+                return lambda: code.decode_ms_soft_batch(x, MAXITERS, app=app[k], output=out[k], iters=it[k], success=ok[k])
+            if k in CASCADE_SOFT:
+                method = code.decode_ms_cascade_soft_batch if k == "cascade_soft_f32" else code.decode_ms_cascade_fixed_soft_batch
+                return lambda: method(x, MAXITERS, app=app[k], output=out[k], iters=it[k], success=ok[k], stage=stage[k])
             if k in CASCADE:
                 if k == "cascade_f32":
                     return lambda: code.decode_ms_cascade_batch(x, MAXITERS, output=out[k], iters=it[k], success=ok[k], stage=stage[k])
@@ -154,14 +177,17 @@ def main():
                          "fer": float(1.0 - succ.double().mean())}
             if key in CASCADE:
                 case[key]["stage2_share"] = float(stage[key].double().mean())
+            if key in CASCADE_SOFT and CASCADE_SOFT[key][0] in keys:
+                case[key]["hard_equals_cascade"] = all(torch.equal(x[key], x[CASCADE_SOFT[key][0]]) for x in (out, it, ok, stage))
         for key in keys:
             for base in ("layered_f32", DECODERS[key][1], "fixed_i8" if key in FIXED_CORRECTED else None, CASCADE.get(key, (None,))[0],
-                         "flooding_f32" if key in FLOODING_CORRECTED else None, "cascade_f32" if key == "cascade_f32_fc" else None):
+                         "flooding_f32" if key in FLOODING_CORRECTED else None, "cascade_f32" if key == "cascade_f32_fc" else None,
+                         *CASCADE_SOFT.get(key, ())):
                 if base in keys and base != key:
                     case[f"{key}_over_{base}"] = round(case[key]["mcw_s"] / case[base]["mcw_s"], 4)
         res["cases"].append(case)
         print(json.dumps(case), file=sys.stderr, flush=True)
-        del llrs, out, it, ok, stage, calls
+        del llrs, out, it, ok, stage, app, calls
         torch.cuda.empty_cache()
     print(json.dumps(res), flush=True)
 
