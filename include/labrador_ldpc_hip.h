@@ -326,7 +326,8 @@ int labrador_ldpc_decode_ms_batch_f64(enum labrador_ldpc_code code, const double
  * 16-byte aligned (and `output` 8-byte aligned).  Kernels (DESIGN.md "Soft output"):
  *   - f32, i16, i32: the soft forms of the hard-only call's kernels -- every variant that call accepts;
  *   - i8: the f32-pipe i8 kernels (those the hard-only call takes for unaligned buffers) whatever the batch size;
- *     LABRADOR_LDPC_HIP_VARIANT_BITSLICE (64) returns LABRADOR_LDPC_HIP_EUNSUPPORTED: the bit-sliced kernels keep no marginals;
+ *     LABRADOR_LDPC_HIP_VARIANT_BITSLICE (64) returns LABRADOR_LDPC_HIP_EUNSUPPORTED here: the bit-sliced kernels' soft form is an
+ *     entry of its own, labrador_ldpc_decode_ms_bitsliced_soft_batch_i8 below (same results, the bit-sliced rate);
  *   - f64: the register kernels, except the in-place ones (variant | LABRADOR_LDPC_HIP_VARIANT_PAIR), which keep only the signs of
  *     most marginals: an explicit in-place variant returns LABRADOR_LDPC_HIP_EUNSUPPORTED, and TM8192, whose tuned f64 kernel is
  *     in place, runs the workspace kernel (LABRADOR_LDPC_HIP_VARIANT_F64_WORKSPACE) by default.
@@ -346,6 +347,25 @@ int labrador_ldpc_decode_ms_soft_batch_i32(enum labrador_ldpc_code code, const i
 int labrador_ldpc_decode_ms_soft_batch_f64(enum labrador_ldpc_code code, const double *llrs, double *app,
                                            uint8_t *output, uint32_t *iters, uint8_t *success,
                                            size_t batch, size_t max_iters, const struct labrador_ldpc_hip_opts *opts);
+
+/* Soft output from the BIT-SLICED i8 kernels.  Per frame, `app`, `output`, `iters` and `success` equal what
+ * labrador_ldpc_decode_ms_soft_batch_i8 returns, bit for bit: the reference's va, saturating, reaching -128; all zero for
+ * max_iters = 0.  The kernel is the lockstep bit-sliced kernel of the code in its soft form -- it keeps the seven magnitude planes of
+ * every block column's marginal beside the hard word and turns them back into bytes at the end -- at EVERY batch size: no crossover to
+ * the f32-pipe kernels, as for labrador_ldpc_decode_ms_corrected_batch_i8.
+ * Codes: TM1536, TM2048, TM6144 and TM8192.  A TC code, and any `variant` but 0, return LABRADOR_LDPC_HIP_EUNSUPPORTED; so do TM1280
+ * and TM5120, whose text says that the two-wave kernels have no soft form.
+ * Rates on one MI355X (device-resident, 2 dB, cap 25), against labrador_ldpc_decode_ms_soft_batch_i8 on the same frames:
+ *   TM8192 18.87 against 8.11 M codewords/s (2.33 x); TM2048 64.6 against 37.0 (1.75 x); TM6144 11.84 against 6.59 (1.80 x); TM1536
+ *   46.7 against 33.4 (1.40 x) -- faster on all four, at 0.83 / 0.82 / 0.64 / 0.64 of the hard lockstep bit-sliced kernel's rate.
+ * Order of the checks: code, empty batch (OK, touches nothing), NULL buffers -- `app` included -- (EINVAL), variant and code family
+ * (EUNSUPPORTED) -- all before any device work.  With LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` must be 4-byte, `output` 8-byte and `app`
+ * 16-byte aligned (EINVAL); the input is always copied in.  Host buffers are staged with `app` as the fourth output; device sets
+ * shard; asynchronous on opts->stream with MEM_DEVICE -- all as labrador_ldpc_decode_ms_soft_batch_i8.
+ * There is no _multi, single-frame, quantised (f32-in), corrected, slot-refill or two-wave form.  Returns a status code. */
+int labrador_ldpc_decode_ms_bitsliced_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int8_t *app, uint8_t *output,
+                                                    uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                    const struct labrador_ldpc_hip_opts *opts);
 
 /* Layered schedule (f32; for i8 and i16 LLRs see the fixed-point calls further down): block-row layered min-sum decoding instead
  * of the reference's flooding schedule.  Block row r of the prototype (a "layer": 4 for the TC codes, 3 for the TM codes) updates
@@ -606,10 +626,11 @@ int labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8(enum labrador_l
  *             comparable only within a stage.
  * max_iters = 0: stage 1 fails every frame with zero marginals, and every frame goes to stage 2 (stage all 1, app the layered
  * decoder's).  max_sweeps = 0: the frames stage 1 failed carry what the layered soft entry returns at cap 0.
- * The integer entries have no stage-1 correction: the corrected bit-sliced kernels have no soft form.  Nor have the plain bit-sliced
- * kernels, so soft i8 on the TM codes runs the f32-pipe i8 kernel, as labrador_ldpc_decode_ms_soft_batch_i8 does: THE FIRST STAGE OF
- * THE i8 SOFT CASCADE ON A TM CODE THEREFORE RUNS AT THE f32-PIPE RATE, not at the bit-sliced rate of the hard cascade (DESIGN.md 4.4,
- * 4.15).  `variant` 64 (the bit-sliced kernels) returns LABRADOR_LDPC_HIP_EUNSUPPORTED with the soft flooding entry's text.
+ * The integer entries have no stage-1 correction: the corrected bit-sliced kernels have no soft form.  Soft i8 on the TM codes runs the
+ * f32-pipe i8 kernel here, as labrador_ldpc_decode_ms_soft_batch_i8 does: THE FIRST STAGE OF THE i8 SOFT CASCADE ON A TM CODE
+ * THEREFORE RUNS AT THE f32-PIPE RATE in this entry, not at the bit-sliced rate of the hard cascade;
+ * labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8 below is the same cascade with the bit-sliced soft kernel as its first stage
+ * (DESIGN.md 4.16).  `variant` 64 (the bit-sliced kernels) returns LABRADOR_LDPC_HIP_EUNSUPPORTED here with the soft flooding entry's text.
  * Checks, in the hard cascade's order and with its texts: `code`; for f32 both pairs, before the batch is looked at; an empty batch
  * is OK and touches nothing; a NULL buffer, `app` and `stage` included, is EINVAL; for i8 / i16 the triple; f32 with a stage-1 pair
  * other than (1, 0) and `variant` != 0 is EUNSUPPORTED -- all before any device work.  With MEM_DEVICE `output` must be 8-byte and
@@ -629,6 +650,19 @@ int labrador_ldpc_decode_ms_cascade_soft_batch_i16(enum labrador_ldpc_code code,
                                                    uint32_t *iters, uint8_t *success, uint8_t *stage, size_t batch, size_t max_iters,
                                                    size_t max_sweeps, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
                                                    const struct labrador_ldpc_hip_opts *opts);
+
+/* labrador_ldpc_decode_ms_cascade_soft_batch_i8 with labrador_ldpc_decode_ms_bitsliced_soft_batch_i8 as stage 1: all
+ * five results equal that entry's bit for bit -- a stage-0 frame's int32 marginal is the sign-extended saturating one -- with the first
+ * stage at the bit-sliced kernels' rate.  That entry's checks, and on top of them: TM1536, TM2048, TM6144 and TM8192 and `variant` 0
+ * only (any other is LABRADOR_LDPC_HIP_EUNSUPPORTED before any device work; TM1280 and TM5120 with the text that the two-wave kernels
+ * have no soft form), and with LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` 4-byte aligned (EINVAL).  Chunking
+ * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and synchronisation as that entry.  There is no _multi, quantised (f32-in) or corrected-stage-1
+ * form.  Returns a status code. */
+int labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app,
+                                                            uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
+                                                            size_t batch, size_t max_iters, size_t max_sweeps, uint32_t scale_num,
+                                                            uint32_t scale_shift, uint32_t offset,
+                                                            const struct labrador_ldpc_hip_opts *opts);
 
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --

@@ -112,6 +112,10 @@ SYMBOLS = {
     "labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _int,
                                                                             _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
                                                                             _c.c_uint32, _optp]),
+    # soft output from the bit-sliced i8 kernels, and the soft i8 cascade with them as stage 1
+    "labrador_ldpc_decode_ms_bitsliced_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
+    "labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32,
+                                                                       _c.c_uint32, _c.c_uint32, _optp]),
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -625,12 +629,21 @@ class LDPCCode(enum.IntEnum):
     def decode_ms_cascade_fixed_soft_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, app=None, output=None,
                                            iters=None, success=None, stage=None, variant: int = 0, stream: Optional[int] = None,
                                            devices=None, scale_num: Optional[int] = None, scale_shift: Optional[int] = None,
-                                           offset: Optional[int] = None):
+                                           offset: Optional[int] = None, bitsliced: bool = False):
         """decode_ms_cascade_fixed_batch with soft output, for int8 and int16 LLRs (labrador_ldpc_decode_ms_cascade_soft_batch_i8 /
         _i16).  `app` is ALWAYS int32: a stage-0 frame holds the flooding decoder's saturating marginal of the LLR
         type, sign-extended; a stage-1 frame the layered decoder's exact sum -- marginals are comparable only within a stage.  There
-        is no first-stage triple, and on a TM code the int8 first stage is the soft flooding kernel, not the bit-sliced one.
+        is no first-stage triple, and on a TM code the int8 first stage is the soft flooding kernel, not the bit-sliced one --
+        unless `bitsliced` asks for it (labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8, DESIGN.md 4.16: the first stage as
+        decode_ms_bitsliced_soft_batch; same results bit for bit; int8 LLRs, TM1536 / TM2048 / TM6144 / TM8192 and `variant` 0 only,
+        device `llrs` 4-byte aligned).
         Returns (app[batch, n + p] int32, output, iters, success, stage)."""
+        if bitsliced:
+            return self._batch_call("labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_", llrs, maxiters, output, iters, success, variant,
+                                    stream, devices, soft=True, app=app, app_dtype="i32",
+                                    extra=(maxiters if max_sweeps is None else max_sweeps,
+                                           *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0))),
+                                    stage=stage, with_stage=True, types=("i8",))
         return self._batch_call("labrador_ldpc_decode_ms_cascade_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
                                 devices, soft=True, app=app, app_dtype="i32",
                                 extra=(maxiters if max_sweeps is None else max_sweeps,
@@ -701,6 +714,16 @@ class LDPCCode(enum.IntEnum):
                                     soft=True, app=app, half=True)
         return self._batch_call("labrador_ldpc_decode_ms_corrected_soft_batch_", llrs, maxiters, output, iters, success, variant, stream,
                                 devices, soft=True, app=app, extra=(float(scale), float(offset)), types=("f32",))
+
+    def decode_ms_bitsliced_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
+                                       stream: Optional[int] = None, devices=None):
+        """decode_ms_soft_batch on int8 LLRs from the bit-sliced kernels (labrador_ldpc_decode_ms_bitsliced_soft_batch_i8, DESIGN.md
+        4.16): the same four results bit for bit -- the marginals saturate as the reference's do and reach -128 -- at the bit-sliced
+        kernels' rate, whatever the batch size.  TM1536, TM2048, TM6144 and TM8192 only: any other code, or any dtype but int8,
+        raises LdpcHipError.  With device buffers `llrs` must be 4-byte and `app` 16-byte aligned.  Buffers, `stream` and `devices`
+        as decode_ms_batch.  Returns (app[batch, n + p] int8 -- punctured variables last --, output, iters, success)."""
+        return self._batch_call("labrador_ldpc_decode_ms_bitsliced_soft_batch_", llrs, maxiters, output, iters, success, 0, stream, devices,
+                                soft=True, app=app, types=("i8",))
 
     def decode_ms_layered_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
                                      variant: int = 0, stream: Optional[int] = None, devices=None, scale: float = 1.0, offset: float = 0.0):

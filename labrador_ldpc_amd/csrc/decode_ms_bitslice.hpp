@@ -53,6 +53,11 @@
 //    scale_shift) - offset, 0) is applied to those two, once per row and iteration, in bit planes (Decoder::correct_mag) -- never per
 //    edge.  The plain instantiations carry nothing of it.
 //
+//  * SOFT OUTPUT (Decoder<..., SOFT = true>; the kernels of decode_ms_bs_soft.hip).  Where an iteration stores a block
+//    column's hard word it keeps the marginal's seven magnitude planes too, under the same rule (a finished codeword of a group keeps
+//    what it has), in registers or in LDS (BsPlan::SOFT_LDS); the epilogue turns the planes back into bytes (store_marginals).  The
+//    plain instantiations carry nothing of it.
+//
 // What an instantiation is built with -- the members named above, per code, with what each was measured at -- stands in BsPlan
 // (decode_ms_bs_plan.hpp); the settings behind it (BS_*) in decode_ms_tuning.hpp.
 #pragma once
@@ -318,6 +323,12 @@ struct Geo {
                          LDS_BYTES = LDS_PRIVATE + (NZ_LDS - NZ_IN_SLAB) * 256;
     static constexpr int nz_addr(int e) { return nz_slot(e) < NZ_IN_SLAB ? LDS_HARD + (NCOLS_OWN + nz_slot(e)) * 256 : LDS_NZ_TAIL + (nz_slot(e) - NZ_IN_SLAB) * 256; }
     static_assert(!SPLIT || NCOLS_OWN * 256 <= LLR_WORDS * 4, "the epilogue's hard-decision words alias the LLR planes");
+    // The soft form (Decoder<..., SOFT>): the MG magnitude planes of every block column's kept marginal (the sign plane is the hard word),
+    // [NCOLS][MG][64] words behind everything above where the plan places them in LDS, else in registers.  Its epilogue's staging slab is
+    // the LLR planes' area, dead by then (the hard-decision words are still read there).
+    static constexpr bool SOFT_LDS = PLAN::SOFT_LDS && !SPLIT;
+    static constexpr int LDS_SOFT = LDS_BYTES, LDS_BYTES_SOFT = LDS_BYTES + (SOFT_LDS ? NCOLS_OWN * MG * 256 : 0);
+    static constexpr int soft_addr(int c, int k) { return LDS_SOFT + (col_slot(c) * MG + k) * 256; }
     static_assert(NCOLS <= 16);
 };
 
@@ -409,7 +420,11 @@ constexpr int correction_mulbits(uint32_t scale_num, uint32_t scale_shift)
     return num == 256u ? 0 : (num & 15u) == 0 ? 4 : 8;
 }
 
-template <int CODE, class B, int HALF = -1, bool CORRECTED = false, int MULBITS = 8>
+// the kept marginal planes of the soft form where they live in registers; nothing otherwise
+template <class V, int NCOLS> struct SoftPlanes { V p[NCOLS][MG]; };
+struct NoSoftPlanes {};
+
+template <int CODE, class B, int HALF = -1, bool CORRECTED = false, int MULBITS = 8, bool SOFT = false>
 struct Decoder {
     using V = typename B::V;
     using GEO = Geo<CODE, HALF>;
@@ -428,6 +443,9 @@ struct Decoder {
     V hard[NCOLS];                      // (unused with Geo::HARD_LDS)
     V fail;                             // OR of the parities of the rows finished in this iteration (decoder.rs:453)
     [[no_unique_address]] std::conditional_t<CORRECTED, Correction, NoCorrection> corr;      // (read only under CORRECTED)
+    static_assert(!SOFT || (HALF < 0 && PL == 8), "the soft form: the one-wave kernels, i8 planes");
+    static constexpr bool SOFT_REGS = SOFT && !GEO::SOFT_LDS;
+    [[no_unique_address]] std::conditional_t<SOFT_REGS, SoftPlanes<V, NCOLS>, NoSoftPlanes> soft;      // (touched only under SOFT)
 
     BS_FN void init_lane(B &b)
     {
@@ -446,6 +464,13 @@ struct Decoder {
     }
 
     BS_FN V hard_addr(int c) const { return B::add(B::shl(lane, 2), B::c(GEO::LDS_HARD + GEO::col_slot(c) * 256)); }
+    BS_FN V soft_addr(int c, int k) const { return B::add(B::shl(lane, 2), B::c(GEO::soft_addr(c, k))); }
+    // SOFT: magnitude plane k of block column c's marginal, as kept by the last iteration that was allowed to (columns())
+    template <int C, int K> BS_FN V kept_plane(B &b) const
+    {
+        if constexpr (SOFT_REGS) return soft.p[C][K];
+        else return b.lds_read32(soft_addr(C, K));
+    }
 
     // decoder.rs:374: the working area is zeroed, so before iteration 0 min1 = min2 = 0, every v = 0, every sign product +.
     // z(x) zeroes a state register, zl(addr) a state word in LDS
@@ -473,6 +498,12 @@ struct Decoder {
             if constexpr (GEO::owns_col(c)) {
                 if constexpr (GEO::HARD_LDS) zl(hard_addr(c));        // (max_iters = 0: all-zero output, decoder.rs:466-473)
                 else z(hard[c]);
+                if constexpr (SOFT)                                   // (max_iters = 0: all-zero marginals, decoder.rs:374)
+                    sfor<0, MG>([&](auto K_) {
+                        constexpr int k = decltype(K_)::value;
+                        if constexpr (SOFT_REGS) z(soft.p[c][k]);
+                        else zl(soft_addr(c, k));
+                    });
             }
         });
     }
@@ -778,6 +809,16 @@ struct Decoder {
                 else b.lds_write32(hard_addr(c), B::select_lanes(frozen, b.lds_read32(hard_addr(c)), va[MG]));   // (branch-free: an EXEC-masked
             } else if constexpr (G == 1) hard[c] = va[MG];                                                        //  store would split the loop body)
             else hard[c] = B::select_lanes(frozen, hard[c], va[MG]);
+            // SOFT: the marginal's other planes under the same rule -- a codeword keeps those of its converging iteration, or of the last one
+            if constexpr (SOFT)
+                sfor<0, MG>([&](auto K_) {
+                    constexpr int k = decltype(K_)::value;
+                    if constexpr (SOFT_REGS) {
+                        if constexpr (G == 1) soft.p[c][k] = va[k];
+                        else soft.p[c][k] = B::select_lanes(frozen, soft.p[c][k], va[k]);
+                    } else if constexpr (G == 1) b.lds_write32(soft_addr(c, k), va[k]);
+                    else b.lds_write32(soft_addr(c, k), B::select_lanes(frozen, b.lds_read32(soft_addr(c, k)), va[k]));
+                });
             // ---- check side of the same edges (decoder.rs:419-447) ----
             sfor<0, NB>([&](auto E_) {
                 constexpr int e = decltype(E_)::value;
@@ -926,31 +967,27 @@ BS_FN void load_column_planes(B &b, const D &d, const int8_t *llrs, int c, uint3
     B::mem_fence();
 }
 
-// the 32 LLR bytes at slab positions p0 + L * bit (bit = 0 .. 31; the slab is skewed) -> the 8 bit planes X[p] of those 32 indices
+// skewed LDS address of the byte at slab position p0 + L * bit
 template <int CODE, class B>
-BS_FN void gather_planes(B &b, typename B::V p0, int stage, typename B::V (&X)[8])
+BS_FN typename B::V slab_byte_addr(typename B::V p0, int stage, int bit)
 {
-    using GEO = Geo<CODE>;
     using V = typename B::V;
-    constexpr int L = GEO::L;
-    auto at = [&](int bit) {                                                                  // skewed LDS address of bit `bit`
-        if constexpr (L * 32 <= 256 && 256 % (L * 32) == 0) {
-            // the lane's 32 bytes lie inside one 256-byte run: one skew for all of them
-            return B::add(B::add(p0, B::shl(B::shr(p0, 8), 4)), B::c(stage + L * bit));
-        } else {
-            const V pp = B::add(p0, B::c(L * bit));
-            return B::add(B::add(pp, B::shl(B::shr(pp, 8), 4)), B::c(stage));
-        }
-    };
-    sfor<0, 8>([&](auto D_) {
-        constexpr int dd = decltype(D_)::value;
-        V x = b.lds_read_u8(at(dd));
-        x = B::or_(x, B::shl(b.lds_read_u8(at(8 + dd)), 8));
-        x = B::or_(x, B::shl(b.lds_read_u8(at(16 + dd)), 16));
-        x = B::or_(x, B::shl(b.lds_read_u8(at(24 + dd)), 24));
-        X[dd] = x;
-    });
-    // 8 x 8 bit-matrix transpose inside every byte lane: afterwards X[p] byte y bit dd = bit p of LLR (8 y + dd)
+    constexpr int L = Geo<CODE>::L;
+    if constexpr (L * 32 <= 256 && 256 % (L * 32) == 0) {
+        // the lane's 32 bytes lie inside one 256-byte run: one skew for all of them
+        return B::add(B::add(p0, B::shl(B::shr(p0, 8), 4)), B::c(stage + L * bit));
+    } else {
+        const V pp = B::add(p0, B::c(L * bit));
+        return B::add(B::add(pp, B::shl(B::shr(pp, 8), 4)), B::c(stage));
+    }
+}
+
+// 8 x 8 bit-matrix transpose inside every byte lane of X[0 .. 7]: bit dd of byte y of X[p] <-> bit p of byte y of X[dd].  Three stages of
+// block swaps on independent index bits: the network is its own inverse.
+template <class B>
+BS_FN void transpose_8x8(typename B::V (&X)[8])
+{
+    using V = typename B::V;
     auto stage_t = [&](auto S_, uint32_t mask) {
         constexpr int s = decltype(S_)::value;
         sfor<0, 8>([&](auto D_) {
@@ -965,6 +1002,76 @@ BS_FN void gather_planes(B &b, typename B::V p0, int stage, typename B::V (&X)[8
     stage_t(IC<4>{}, 0x0F0F0F0Fu);
     stage_t(IC<2>{}, 0x33333333u);
     stage_t(IC<1>{}, 0x55555555u);
+}
+
+// the 32 LLR bytes at slab positions p0 + L * bit (bit = 0 .. 31; the slab is skewed) -> the 8 bit planes X[p] of those 32 indices
+template <int CODE, class B>
+BS_FN void gather_planes(B &b, typename B::V p0, int stage, typename B::V (&X)[8])
+{
+    using V = typename B::V;
+    auto at = [&](int bit) { return slab_byte_addr<CODE, B>(p0, stage, bit); };
+    sfor<0, 8>([&](auto D_) {
+        constexpr int dd = decltype(D_)::value;
+        V x = b.lds_read_u8(at(dd));
+        x = B::or_(x, B::shl(b.lds_read_u8(at(8 + dd)), 8));
+        x = B::or_(x, B::shl(b.lds_read_u8(at(16 + dd)), 16));
+        x = B::or_(x, B::shl(b.lds_read_u8(at(24 + dd)), 24));
+        X[dd] = x;
+    });
+    // afterwards X[p] byte y bit dd = bit p of LLR (8 y + dd)
+    transpose_8x8<B>(X);
+}
+
+// ---- the soft form's epilogue: the inverse of load_column_planes ----
+// the 8 bit planes X[p] of a lane's 32 indices -> their 32 bytes at slab positions p0 + L * bit
+template <int CODE, class B>
+BS_FN void scatter_planes(B &b, typename B::V p0, int stage, typename B::V (&X)[8])
+{
+    transpose_8x8<B>(X);                                             // afterwards X[dd] byte y = the value of index 8 y + dd
+    sfor<0, 8>([&](auto D_) {
+        constexpr int dd = decltype(D_)::value;
+        sfor<0, 4>([&](auto Y_) {
+            constexpr int y = decltype(Y_)::value;
+            b.lds_write8(slab_byte_addr<CODE, B>(p0, stage, 8 * y + dd), B::shr(X[dd], 8 * y));
+        });
+    });
+}
+
+// The kept marginals of a group -> app [frame][NP] i8, variable j = c * M + index (the punctured block columns are the last ones).
+// Block column by block column: the lane's eight planes -- seven kept ones and the hard word, which is the sign plane -- become the 32
+// bytes of its indices in the skewed slab (the LLR planes' area, dead after the iterations), and the slab leaves as it came: two
+// 16-byte rows per lane, consecutive lanes consecutive bytes, masked by the frame's validity.  -128 stays -128: the planes are the
+// saturating sum's (Arith::sat_add_x).
+template <int CODE, class B, class D>
+BS_FN void store_marginals(B &b, const D &d, int8_t *app, uint32_t group, uint32_t batch)
+{
+    using GEO = Geo<CODE>;
+    using V = typename B::V;
+    constexpr int M = GEO::M, NP = GEO::NP, Q = GEO::Q, W = GEO::W, G = GEO::G, NCOLS = GEO::NCOLS, stage = GEO::LDS_LLR;
+    static_assert(GEO::LLR_WORDS * 4 >= STAGE_BYTES && GEO::LDS_LLR % 16 == 0, "the slab fits the LLR planes' area");
+    static_assert(NP % 16 == 0 && M % 16 == 0, "16-byte rows of app");
+    const V cw = B::shr(d.lane, ilog2c(W));
+    const V p0 = B::add(B::add(B::shl(cw, ilog2c(M)), B::shl(d.q, ilog2c(Q))), d.ll);       // position of bit 0
+    sfor<0, NCOLS>([&](auto C_) {
+        constexpr int c = decltype(C_)::value;
+        V X[8];
+        sfor<0, MG>([&](auto K_) { constexpr int k = decltype(K_)::value; X[k] = d.template kept_plane<c, k>(b); });
+        X[MG] = b.lds_read32(d.hard_addr(c));
+        // (compiler fences around the slab's use: byte stores and 16-byte vector loads of the same LDS bytes -- see load_column_planes)
+        B::mem_fence();
+        scatter_planes<CODE>(b, p0, stage, X);
+        B::mem_fence();
+        sfor<0, 2>([&](auto H_) {
+            constexpr int h = decltype(H_)::value;
+            const V p = B::add(B::shl(d.lane, 4), B::c(1024 * h));                           // slab position of the lane's 16 bytes
+            const V pcw = B::shr(p, ilog2c(M));                                               // their codeword inside the group
+            const V ok = B::less_u(B::add(B::c(group * (uint32_t)G), pcw), B::c(batch));
+            V w[4];
+            b.lds_read128(B::add(B::add(p, B::shl(B::shr(p, 8), 4)), B::c(stage)), w);      // stage_skew(p)
+            b.gstore128(app, B::add(B::mul_u(pcw, (uint32_t)NP), B::add(B::c((uint32_t)c * M), B::and_(p, B::c(M - 1)))), w, ok);
+        });
+        B::mem_fence();
+    });
 }
 
 // the lanes of codeword (slot) g of a wave that holds 64 / W codewords, as a lane mask
@@ -1007,14 +1114,16 @@ BS_FN void init_kernel(B &b)
 // ---- driver: one wave decodes group after group of G codewords ---------------------------------------------------------------
 // llrs [batch][N] i8, output [batch][NP/8] MSB first, iters [batch], success [batch]; `group` = index of the group of G frames.
 // (Lane offsets are relative to the group's first frame, so they fit 32 bits whatever the batch.)
-template <int CODE, class B, bool CORRECTED = false, int MULBITS = 8>
+// SOFT: app [batch][NP] i8 receives every frame's marginals as well (store_marginals).
+template <int CODE, class B, bool CORRECTED = false, int MULBITS = 8, bool SOFT = false>
 BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint32_t *iters_all, uint8_t *success_all, uint32_t batch,
-                        uint32_t maxiters, uint32_t group, uint32_t scale_num = 1, uint32_t scale_shift = 0, uint32_t offset = 0)
+                        uint32_t maxiters, uint32_t group, uint32_t scale_num = 1, uint32_t scale_shift = 0, uint32_t offset = 0,
+                        int8_t *app_all = nullptr)
 {
     using GEO = Geo<CODE>;
     using V = typename B::V;
     constexpr int M = GEO::M, W = GEO::W, G = GEO::G, NTX = GEO::NTX, NCOLS = GEO::NCOLS;
-    Decoder<CODE, B, -1, CORRECTED, MULBITS> d;
+    Decoder<CODE, B, -1, CORRECTED, MULBITS, SOFT> d;
     if constexpr (CORRECTED) d.corr = Correction{scale_num, scale_shift, offset};
     d.init_lane(b);
     const V lane = d.lane;
@@ -1087,6 +1196,7 @@ BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint3
     const V first = B::and_(valid2, B::eq(lw2, B::c(0)));
     b.gstore32(iters, B::shl(cw2, 2), iters_v, first);
     b.gstore8(success, cw2, ok_v, first);
+    if constexpr (SOFT) store_marginals<CODE>(b, d, app_all + (size_t)group * G * GEO::NP, group, batch);
 }
 
 

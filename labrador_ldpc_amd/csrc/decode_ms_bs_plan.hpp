@@ -14,6 +14,10 @@ namespace bs {
 // the codes the bit-sliced kernels exist for: the CCSDS TM (AR4JA) codes.  (The TC codes' circulants are not quarter-wise rotations.)
 constexpr bool bitsliced_code(int code) { return code >= TM1280 && code <= TM8192; }
 
+// the codes the soft-output form of those kernels exists for (decode_ms_bs_soft.hip): the one-wave codes -- not the two rate-4/5 codes,
+// whose two-wave kernels have none
+constexpr bool bitsliced_soft_code(int code) { return code == TM1536 || code == TM2048 || code == TM6144 || code == TM8192; }
+
 enum class Rate { R12, R23, R45 };
 
 template <int CODE>
@@ -85,6 +89,20 @@ struct BsPlan {
     // kernels (168 registers, spilling) 2.5 % (profiles/r05_kbench/permute_pipeline.txt, section 7).
     static constexpr int UNIT = per_rate(1, 2, 2);
 
+    // SOFT_LDS, SOFT_WAVES_PER_SIMD: the soft form (Decoder<..., SOFT>, decode_ms_bs_soft.hip) keeps the seven magnitude
+    // planes of every block column's marginal beside the hard word: NCOLS x 7 planes, 35 (rate 1/2) or 49 (rate 2/3) -- in REGISTERS, or
+    // in LDS behind the wave's other areas (NCOLS x 7 x 256 bytes: 8 960 / 12 544), written once per iteration and column (read and
+    // selected as well where a wave holds several codewords).
+    // Rate 1/2: REGISTERS, at two waves per SIMD (196 / 212 registers, no spill; LDS stays the plain kernel's): TM8192 18.87, TM2048
+    // 64.61 M codewords/s.  In LDS the wave needs 21 504 bytes -- seven waves per CU, stated as one per SIMD -- and pays the LDS
+    // traffic: 16.55 / 56.61.
+    // Rate 2/3: the plain kernels need 233 registers at two waves per SIMD, so 49 more planes exist only at ONE wave per SIMD (283
+    // registers) or in LDS -- 30 720 bytes per wave, five waves per CU, which the launch bounds can only state as one per SIMD as well
+    // (two would promise eight).  LDS: TM6144 11.84, TM1536 46.73; registers at one wave per SIMD 11.02 / 43.71.
+    // (One MI355X, 2 dB, cap 25, tools/bs_soft_rate.py: DESIGN.md 4.16 and docs/experiments.md.)
+    static constexpr bool SOFT_LDS = per_rate(BS_SOFT_LDS_R12, BS_SOFT_LDS_R23, 0) != 0;
+    static constexpr int SOFT_WAVES_PER_SIMD = per_rate(SOFT_LDS ? 1 : 2, 1, 0);         // (0: the two-wave kernels have no soft form)
+
     // MIN_GROUPS: groups of G codewords from which the bit-sliced kernel is faster per call than the f32-pipe kernels, which it then
     // replaces in the default dispatch (tools/bs_crossover.py, profiles/r05_kbench/bs_crossover.txt: TM8192 and TM1280 cross at 1024
     // groups, TM6144 and TM5120 at 768, TM2048 and TM1536 at 2048)
@@ -117,6 +135,8 @@ static_assert(BsPlan<TM2048>::WAVES_PER_SIMD == 3 && BsPlan<TM8192>::WAVES_PER_S
               "rate 1/2 builds at 3 waves per SIMD, the rest at 2");
 static_assert(BsPlan<TM2048>::UNIT == 1 && BsPlan<TM8192>::UNIT == 1 && BsPlan<TM1280>::UNIT == 2 && BsPlan<TM1536>::UNIT == 2 &&
               BsPlan<TM5120>::UNIT == 2 && BsPlan<TM6144>::UNIT == 2, "TM2048 and TM8192 in unit 1, the rest in unit 2");
+static_assert(!BsPlan<TM2048>::SOFT_LDS && !BsPlan<TM8192>::SOFT_LDS && BsPlan<TM1536>::SOFT_LDS && BsPlan<TM6144>::SOFT_LDS,
+              "the soft form keeps its planes in registers on rate 1/2, in LDS on rate 2/3");
 #endif
 
 }  // namespace bs

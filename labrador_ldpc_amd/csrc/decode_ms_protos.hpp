@@ -34,6 +34,12 @@ hipError_t launch_decode_ms_bitsliced_corrected(int code, const int8_t *llrs, ui
                                                 uint32_t maxiters, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
                                                 hipStream_t stream);
 
+// The bit-sliced i8 flooding kernels of the one-wave TM codes with soft output (decode_ms_bs_soft.hip): app [batch][n + p]
+// i8, the saturating marginals, beside the three hard results.  The lockstep soft kernel at every batch size; llrs and output 4-byte,
+// app 16-byte aligned (the caller checks).  hipErrorInvalidConfiguration for any other code (bs::bitsliced_soft_code).
+hipError_t launch_decode_ms_bitsliced_soft(int code, const int8_t *llrs, int8_t *app, uint8_t *output, uint32_t *iters, uint8_t *success,
+                                           size_t batch, uint32_t maxiters, hipStream_t stream);
+
 // The flooding schedule on f32 LLRs with normalized / offset check messages (decode_ms_flooding_corrected_f32.hip):
 // the code's default f32 kernel with the correction step; scale and offset are the caller's, already range-checked (capi.hip).
 // app == nullptr launches the hard form.  `variant` 0 only: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).

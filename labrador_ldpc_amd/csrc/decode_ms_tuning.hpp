@@ -15,7 +15,7 @@
     defined(LDPC_PAIR_DEFER_LOCAL) || defined(LDPC_PAIR_DEFER_LOCAL_F32) || defined(LDPC_PAIR_LOCAL_IN_VAR_DEFER) || \
     defined(BS_PLANES) || defined(BS_PIPE) || defined(BS_KEEP_SPLIT) || defined(BS_KEEP_R23) || defined(BS_KEEP_R12) || \
     defined(BS_PINNED_R12) || defined(BS_PINNED_R23) || defined(BS_PINNED_SPLIT) || defined(BS_HARD_LDS) || defined(BS_NZ_LDS) || defined(BS_WAVES_R12) || \
-    defined(BS_REFILL_TM5120) || defined(BS_REFILL_R12)
+    defined(BS_REFILL_TM5120) || defined(BS_REFILL_R12) || defined(BS_SOFT_LDS_R12) || defined(BS_SOFT_LDS_R23)
 #error "the LDPC_* and BS_* tuning switches are fixed in a library build (kernel experiments: tools/kbench/, tools/bs_alt_build.sh)"
 #endif
 #endif
@@ -194,4 +194,11 @@
 #endif
 #ifndef BS_REFILL_R12
 #define BS_REFILL_R12 0
+#endif
+// The soft form's kept marginal planes (BsPlan::SOFT_LDS), per class of kernel: 0 = in registers, 1 = in LDS.
+#ifndef BS_SOFT_LDS_R12
+#define BS_SOFT_LDS_R12 0
+#endif
+#ifndef BS_SOFT_LDS_R23
+#define BS_SOFT_LDS_R23 1
 #endif

@@ -53,6 +53,13 @@ struct HipBackend {
     BS_FN V lds_read_u16(V addr) const { return *reinterpret_cast<const uint16_t *>(lds + addr); }
     BS_FN void lds_write16(V addr, V v) { *reinterpret_cast<uint16_t *>(lds + addr) = (uint16_t)v; }
     BS_FN void lds_write32_if(V addr, V v, V pred) { if (pred) *reinterpret_cast<uint32_t *>(lds + addr) = v; }
+    BS_FN void lds_write8(V addr, V v) { *reinterpret_cast<uint8_t *>(lds + addr) = (uint8_t)v; }      // the low byte of v
+    BS_FN void lds_read128(V addr, V (&w)[4]) const                    // 16-byte aligned
+    {
+        typedef uint32_t u4a __attribute__((ext_vector_type(4)));
+        const u4a v = *reinterpret_cast<const u4a *>(lds + addr);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
     static BS_FN V gload32(const void *p, V off, V pred)
     {
         return pred ? *reinterpret_cast<const uint32_t *>(static_cast<const char *>(p) + off) : 0u;
@@ -77,6 +84,12 @@ struct HipBackend {
     }
     static BS_FN void gstore32(void *p, V off, V v, V pred) { if (pred) *reinterpret_cast<uint32_t *>(static_cast<char *>(p) + off) = v; }
     static BS_FN void gstore32_stream(void *p, V off, V v, V pred) { if (pred) __builtin_nontemporal_store(v, reinterpret_cast<uint32_t *>(static_cast<char *>(p) + off)); }
+    // 16 bytes per lane at a 16-byte-aligned address, written once and not read again by the kernel: a non-temporal stream
+    static BS_FN void gstore128(void *p, V off, const V (&w)[4], V pred)
+    {
+        typedef uint32_t u4a __attribute__((ext_vector_type(4)));
+        if (pred) __builtin_nontemporal_store(u4a{w[0], w[1], w[2], w[3]}, reinterpret_cast<u4a *>(static_cast<char *>(p) + off));
+    }
     static BS_FN void gstore8(void *p, V off, V v, V pred) { if (pred) static_cast<uint8_t *>(p)[off] = (uint8_t)v; }
     // lane-wise select by a 64-bit lane mask: one v_cndmask_b32 with the mask in an SGPR pair, no plane of the mask in a register
     static BS_FN V select_lanes(uint64_t m, V a, V b)
