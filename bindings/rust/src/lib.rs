@@ -148,6 +148,8 @@ extern "C" {
     pub fn labrador_ldpc_decode_ms_cascade_soft_batch_i16(code: LDPCCode, llrs: *const i16, app: *mut i32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_bitsliced_soft_batch_i8(code: LDPCCode, llrs: *const i8, app: *mut i8, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8(code: LDPCCode, llrs: *const i8, app: *mut i32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8(code: LDPCCode, llrs: *const i8, app: *mut i8, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8(code: LDPCCode, llrs: *const i8, app: *mut i32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, flooding_scale_num: u32, flooding_scale_shift: u32, flooding_offset: u32, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_cascade_batch_i8(code: LDPCCode, llrs: *const i8, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_cascade_batch_i16(code: LDPCCode, llrs: *const i16, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_batch_f32_multi(code: LDPCCode, n_parts: usize, devices: *const c_int, llrs: *const *const f32, output: *const *mut u8, iters: *const *mut u32, success: *const *mut u8, frames: *const usize, max_iters: usize, variant: c_int) -> c_int;

@@ -362,10 +362,32 @@ int labrador_ldpc_decode_ms_soft_batch_f64(enum labrador_ldpc_code code, const d
  * (EUNSUPPORTED) -- all before any device work.  With LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` must be 4-byte, `output` 8-byte and `app`
  * 16-byte aligned (EINVAL); the input is always copied in.  Host buffers are staged with `app` as the fourth output; device sets
  * shard; asynchronous on opts->stream with MEM_DEVICE -- all as labrador_ldpc_decode_ms_soft_batch_i8.
- * There is no _multi, single-frame, quantised (f32-in), corrected, slot-refill or two-wave form.  Returns a status code. */
+ * The form with normalized / offset check messages is labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8 below.  There is no
+ * _multi, single-frame, quantised (f32-in), slot-refill or two-wave form.  Returns a status code. */
 int labrador_ldpc_decode_ms_bitsliced_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int8_t *app, uint8_t *output,
                                                     uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
                                                     const struct labrador_ldpc_hip_opts *opts);
+
+/* Soft output from the bit-sliced i8 kernels WITH normalized / offset check messages: the entry above at a triple.
+ * Per frame, `output`, `iters` and `success` equal what labrador_ldpc_decode_ms_corrected_batch_i8 returns at the same
+ * (scale_num, scale_shift, offset), bit for bit, and
+ *   app  [batch][n + p] int8   is the marginal va of that corrected decoder: saturating, reaching -128; all zero for max_iters = 0;
+ *                              punctured variables last.  A converged frame carries va of its converging iteration, any other frame va
+ *                              of the last iteration.
+ * The triple's meaning and ranges are labrador_ldpc_decode_ms_corrected_batch_i8's: scale_shift <= 8, 1 <= scale_num <= 1 <<
+ * scale_shift, offset <= 127 (EINVAL otherwise).  At an identity triple -- (1, 0, 0), or any (1 << s, s, 0) -- the entry still runs
+ * its own kernel, in the offset-only form, and all four results equal labrador_ldpc_decode_ms_bitsliced_soft_batch_i8's bit for bit.
+ * Kernels: the lockstep soft kernels of TM1536, TM2048, TM6144 and TM8192 with the correction step, one form per multiplier width as
+ * for the hard corrected entry, at every batch size.  Rates: DESIGN.md 4.18.
+ * Order of the checks: code, empty batch (OK, touches nothing), NULL buffers -- `app` included -- (EINVAL), the triple (EINVAL),
+ * variant and code family (EUNSUPPORTED, with the texts of labrador_ldpc_decode_ms_bitsliced_soft_batch_i8: TM1280 and TM5120 are told
+ * that the two-wave kernels have no soft form) -- all before any device work.  With LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` must be
+ * 4-byte, `output` 8-byte and `app` 16-byte aligned (EINVAL).  Memory modes, device sets and `stream` as that entry.
+ * There is no _multi, single-frame, quantised (f32-in), slot-refill or two-wave form.  Returns a status code. */
+int labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int8_t *app,
+                                                              uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
+                                                              size_t max_iters, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
+                                                              const struct labrador_ldpc_hip_opts *opts);
 
 /* Layered schedule (f32; for i8 and i16 LLRs see the fixed-point calls further down): block-row layered min-sum decoding instead
  * of the reference's flooding schedule.  Block row r of the prototype (a "layer": 4 for the TC codes, 3 for the TM codes) updates
@@ -626,7 +648,8 @@ int labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8(enum labrador_l
  *             comparable only within a stage.
  * max_iters = 0: stage 1 fails every frame with zero marginals, and every frame goes to stage 2 (stage all 1, app the layered
  * decoder's).  max_sweeps = 0: the frames stage 1 failed carry what the layered soft entry returns at cap 0.
- * The integer entries have no stage-1 correction: the corrected bit-sliced kernels have no soft form.  Soft i8 on the TM codes runs the
+ * The integer entries here take no stage-1 correction (labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8 below is the
+ * i8 soft cascade that does).  Soft i8 on the TM codes runs the
  * f32-pipe i8 kernel here, as labrador_ldpc_decode_ms_soft_batch_i8 does: THE FIRST STAGE OF THE i8 SOFT CASCADE ON A TM CODE
  * THEREFORE RUNS AT THE f32-PIPE RATE in this entry, not at the bit-sliced rate of the hard cascade;
  * labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8 below is the same cascade with the bit-sliced soft kernel as its first stage
@@ -656,13 +679,33 @@ int labrador_ldpc_decode_ms_cascade_soft_batch_i16(enum labrador_ldpc_code code,
  * stage at the bit-sliced kernels' rate.  That entry's checks, and on top of them: TM1536, TM2048, TM6144 and TM8192 and `variant` 0
  * only (any other is LABRADOR_LDPC_HIP_EUNSUPPORTED before any device work; TM1280 and TM5120 with the text that the two-wave kernels
  * have no soft form), and with LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` 4-byte aligned (EINVAL).  Chunking
- * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and synchronisation as that entry.  There is no _multi, quantised (f32-in) or corrected-stage-1
- * form.  Returns a status code. */
+ * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and synchronisation as that entry.  The form with a stage-1 triple is
+ * labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8 below.  There is no _multi or quantised (f32-in) form.  Returns a
+ * status code. */
 int labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app,
                                                             uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
                                                             size_t batch, size_t max_iters, size_t max_sweeps, uint32_t scale_num,
                                                             uint32_t scale_shift, uint32_t offset,
                                                             const struct labrador_ldpc_hip_opts *opts);
+
+/* The entry above with a STAGE-1 TRIPLE: labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8 at
+ * (flooding_scale_num, flooding_scale_shift, flooding_offset) and cap max_iters as stage 1, then, on the original LLRs of the frames
+ * it failed, labrador_ldpc_decode_ms_layered_fixed_corrected_soft_batch_i8 at (scale_num, scale_shift, offset) and cap max_sweeps --
+ * per frame exactly the composition of those two calls.  `output`, `iters`, `success` and `stage` equal, bit for bit, what
+ * labrador_ldpc_decode_ms_cascade_corrected_batch_i8 returns for the same arguments; `app` is int32 as for the other integer soft
+ * cascades: a stage-0 row is the corrected flooding decoder's saturating int8 marginal sign-extended, a stage-1 row the layered
+ * decoder's exact sum.  An identity stage-1 triple runs the plain bit-sliced soft kernel, i.e. the entry above.
+ * Checks: both triples where labrador_ldpc_decode_ms_cascade_corrected_batch_i8 checks them, stage 1's first (EINVAL); then TM1536,
+ * TM2048, TM6144 and TM8192 and `variant` 0 only, with the texts of the entry above (EUNSUPPORTED) -- all before any device work; with
+ * LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` 4-byte, `output` 8-byte and `app` 16-byte aligned (EINVAL).  Chunking
+ * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and synchronisation as the entry above.  There is no _multi or quantised (f32-in) form.  Returns a
+ * status code. */
+int labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app,
+                                                                      uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
+                                                                      size_t batch, size_t max_iters, size_t max_sweeps,
+                                                                      uint32_t flooding_scale_num, uint32_t flooding_scale_shift,
+                                                                      uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
+                                                                      uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
 
 /* Device-resident batches on SEVERAL GPUs with one call (the reference's analogue: one job over all workers,
  * perftest/src/main.rs:39-52; capi/src/lib.rs:83-95 for the buffers' meaning).  Part i is frames[i] frames whose four buffers --

@@ -116,6 +116,12 @@ SYMBOLS = {
     "labrador_ldpc_decode_ms_bitsliced_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_uint32,
                                                                        _c.c_uint32, _c.c_uint32, _optp]),
+    # ... with normalized / offset check messages: the corrected soft kernels, and the soft i8 cascade with a stage-1 triple
+    "labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_uint32, _c.c_uint32,
+                                                                         _c.c_uint32, _optp]),
+    "labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz,
+                                                                                 _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
+                                                                                 _c.c_uint32, _c.c_uint32, _optp]),
     **{f"labrador_ldpc_decode_ms_batch_{t}_multi": (_int, [_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _int]) for t in ("i8", "i16", "i32", "f32", "f64")},
     "labrador_ldpc_decode_bf_batch": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]),
     "labrador_ldpc_encode_batch": (_int, [_int, _vp, _vp, _sz, _optp]),
@@ -343,6 +349,12 @@ def _check_result_buffer(buf, like, shape, kinds, name: str):
 # (submatrix_size, circulant_size) per code: src/codes/mod.rs:109-241
 _SUBMATRIX = {0: (16, 16), 1: (32, 32), 2: (64, 64), 3: (128, 32), 4: (256, 64), 5: (512, 128),
               6: (512, 128), 7: (1024, 256), 8: (2048, 512)}
+
+
+class StageOneTripleError(ValueError, TypeError):
+    """decode_ms_cascade_fixed_soft_batch was given a flooding_* keyword without bitsliced=True.  A ValueError -- the keywords exist,
+    the combination does not -- that is a TypeError as well, which is what the call raised while the method had no such keywords:
+    a caller that catches either keeps working."""
 
 
 def _fixed_correction(scale_num, scale_shift, offset):
@@ -629,7 +641,9 @@ class LDPCCode(enum.IntEnum):
     def decode_ms_cascade_fixed_soft_batch(self, llrs, maxiters: int = 50, max_sweeps: Optional[int] = None, app=None, output=None,
                                            iters=None, success=None, stage=None, variant: int = 0, stream: Optional[int] = None,
                                            devices=None, scale_num: Optional[int] = None, scale_shift: Optional[int] = None,
-                                           offset: Optional[int] = None, bitsliced: bool = False):
+                                           offset: Optional[int] = None, bitsliced: bool = False,
+                                           flooding_scale_num: Optional[int] = None, flooding_scale_shift: Optional[int] = None,
+                                           flooding_offset: Optional[int] = None):
         """decode_ms_cascade_fixed_batch with soft output, for int8 and int16 LLRs (labrador_ldpc_decode_ms_cascade_soft_batch_i8 /
         _i16).  `app` is ALWAYS int32: a stage-0 frame holds the flooding decoder's saturating marginal of the LLR
         type, sign-extended; a stage-1 frame the layered decoder's exact sum -- marginals are comparable only within a stage.  There
@@ -637,7 +651,22 @@ class LDPCCode(enum.IntEnum):
         unless `bitsliced` asks for it (labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8, DESIGN.md 4.16: the first stage as
         decode_ms_bitsliced_soft_batch; same results bit for bit; int8 LLRs, TM1536 / TM2048 / TM6144 / TM8192 and `variant` 0 only,
         device `llrs` 4-byte aligned).
+
+        `flooding_scale_num`, `flooding_scale_shift`, `flooding_offset`: with `bitsliced`, the first stage as
+        decode_ms_bitsliced_soft_batch at that triple (labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8, DESIGN.md
+        4.18); the four hard results are decode_ms_cascade_fixed_batch's at the same arguments.  Without `bitsliced` a ValueError
+        (StageOneTripleError, also a TypeError as before the keywords existed): a corrected soft first stage exists only bit-sliced.  None given: the entries above.
         Returns (app[batch, n + p] int32, output, iters, success, stage)."""
+        flooding = _fixed_correction(flooding_scale_num, flooding_scale_shift, flooding_offset)
+        if flooding is not None:
+            if not bitsliced:
+                raise StageOneTripleError("a corrected soft first stage exists only bit-sliced: flooding_scale_num, flooding_scale_shift "
+                                          "and flooding_offset need bitsliced=True")
+            return self._batch_call("labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_", llrs, maxiters, output, iters, success,
+                                    variant, stream, devices, soft=True, app=app, app_dtype="i32",
+                                    extra=(maxiters if max_sweeps is None else max_sweeps, *flooding,
+                                           *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0))),
+                                    stage=stage, with_stage=True, types=("i8",))
         if bitsliced:
             return self._batch_call("labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_", llrs, maxiters, output, iters, success, variant,
                                     stream, devices, soft=True, app=app, app_dtype="i32",
@@ -716,12 +745,21 @@ class LDPCCode(enum.IntEnum):
                                 devices, soft=True, app=app, extra=(float(scale), float(offset)), types=("f32",))
 
     def decode_ms_bitsliced_soft_batch(self, llrs, maxiters: int = 50, app=None, output=None, iters=None, success=None,
-                                       stream: Optional[int] = None, devices=None):
+                                       stream: Optional[int] = None, devices=None, scale_num: Optional[int] = None,
+                                       scale_shift: Optional[int] = None, offset: Optional[int] = None):
         """decode_ms_soft_batch on int8 LLRs from the bit-sliced kernels (labrador_ldpc_decode_ms_bitsliced_soft_batch_i8, DESIGN.md
         4.16): the same four results bit for bit -- the marginals saturate as the reference's do and reach -128 -- at the bit-sliced
         kernels' rate, whatever the batch size.  TM1536, TM2048, TM6144 and TM8192 only: any other code, or any dtype but int8,
         raises LdpcHipError.  With device buffers `llrs` must be 4-byte and `app` 16-byte aligned.  Buffers, `stream` and `devices`
-        as decode_ms_batch.  Returns (app[batch, n + p] int8 -- punctured variables last --, output, iters, success)."""
+        as decode_ms_batch.  Returns (app[batch, n + p] int8 -- punctured variables last --, output, iters, success).
+
+        `scale_num`, `scale_shift`, `offset`: normalized / offset min-sum, the triple as decode_ms_layered_fixed_batch resolves it
+        (labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8): output, iters and success are
+        decode_ms_corrected_fixed_batch's at that triple and `app` is that decoder's marginal.  None given: the entry above."""
+        extra = _fixed_correction(scale_num, scale_shift, offset)
+        if extra is not None:
+            return self._batch_call("labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_", llrs, maxiters, output, iters, success, 0, stream,
+                                    devices, soft=True, app=app, extra=extra, types=("i8",))
         return self._batch_call("labrador_ldpc_decode_ms_bitsliced_soft_batch_", llrs, maxiters, output, iters, success, 0, stream, devices,
                                 soft=True, app=app, types=("i8",))
 

@@ -40,6 +40,13 @@ hipError_t launch_decode_ms_bitsliced_corrected(int code, const int8_t *llrs, ui
 hipError_t launch_decode_ms_bitsliced_soft(int code, const int8_t *llrs, int8_t *app, uint8_t *output, uint32_t *iters, uint8_t *success,
                                            size_t batch, uint32_t maxiters, hipStream_t stream);
 
+// The same kernels with normalized / offset check messages as well (decode_ms_bs_corrected_soft.hip): app is the
+// saturating marginal of the corrected decoder at the caller's triple (already range-checked), the hard three are
+// launch_decode_ms_bitsliced_corrected's.  The identity triple runs the offset-only form.  Alignments and codes as above.
+hipError_t launch_decode_ms_bitsliced_corrected_soft(int code, const int8_t *llrs, int8_t *app, uint8_t *output, uint32_t *iters,
+                                                     uint8_t *success, size_t batch, uint32_t maxiters, uint32_t scale_num,
+                                                     uint32_t scale_shift, uint32_t offset, hipStream_t stream);
+
 // The flooding schedule on f32 LLRs with normalized / offset check messages (decode_ms_flooding_corrected_f32.hip):
 // the code's default f32 kernel with the correction step; scale and offset are the caller's, already range-checked (capi.hip).
 // app == nullptr launches the hard form.  `variant` 0 only: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).
