@@ -860,6 +860,38 @@ int labrador_ldpc_decode_ms_cascade_quantised_batch_i16(enum labrador_ldpc_code 
                                                         size_t max_sweeps, float scale, int lim, uint32_t scale_num,
                                                         uint32_t scale_shift, uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
 
+/* f32 LLRs through the bit-sliced i8 flooding kernels' OWN LOADER: the quantiser sits where the kernel reads its
+ * LLRs, so there is no quantised copy of the batch, no workspace and no chunk loop -- one launch per slice, and with MEM_DEVICE the
+ * first two calls are asynchronous on opts->stream with nothing to wait for.  Per frame f, exactly,
+ *     _bitsliced_quantised_batch_i8             labrador_ldpc_decode_ms_batch_i8
+ *     _bitsliced_quantised_corrected_batch_i8   labrador_ldpc_decode_ms_corrected_batch_i8 at (scale_num, scale_shift, offset)
+ *     _cascade_bitsliced_quantised_batch_i8     labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8 at the same arguments
+ * on (labrador_ldpc_quantise_llrs_batch_i8 of frame f at (scale, lim)) at cap max_iters: output, iters, success -- and `stage` -- are
+ * that entry's, bit for bit, for every f32 input, +-0, +-inf, NaN (an erasure), denormals and ties included.  An identity triple
+ * (1 << k, k, 0) runs the plain kernel.  The cascade's stage 1 reads the caller's f32 rows, the failed frames' f32 rows are gathered
+ * through the cascade's workspace (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and stage 2 is the fixed-point layered decoder whose loader
+ * quantises (labrador_ldpc_decode_ms_layered_quantised_batch_i8) at the stage-2 triple; like every cascade it SYNCHRONISES
+ * opts->stream once per launch slice and must not be called on a stream that is being captured into a graph.
+ * Lockstep kernels of the four one-wave codes TM1536, TM2048, TM6144 and TM8192 at every batch size, kernel variant 0 only.
+ * Arguments are checked in this order, all before any device work: `code`; `scale` and `lim`; an empty batch is OK whatever the
+ * pointers; a NULL buffer (`stage` included, where the entry has it); opts->variant != 0, a TC code, TM1280 or TM5120 is
+ * EUNSUPPORTED; the ranges of the triples, stage 1's first.  With MEM_DEVICE `output` must be 8-byte and `llrs` 16-byte aligned.
+ * Host f32 rows go through the one batched call path and cross the link as f32; device sets shard the frames as for every batched
+ * entry.  Hard output only.  The older quantised entries keep their two-pass route.  Returns a status code. */
+int labrador_ldpc_decode_ms_bitsliced_quantised_batch_i8(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
+                                                         uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
+                                                         const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_bitsliced_quantised_corrected_batch_i8(enum labrador_ldpc_code code, const float *llrs, uint8_t *output,
+                                                                   uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                                   float scale, int lim, uint32_t scale_num, uint32_t scale_shift,
+                                                                   uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_i8(enum labrador_ldpc_code code, const float *llrs, uint8_t *output,
+                                                                 uint32_t *iters, uint8_t *success, uint8_t *stage, size_t batch,
+                                                                 size_t max_iters, size_t max_sweeps, float scale, int lim,
+                                                                 uint32_t flooding_scale_num, uint32_t flooding_scale_shift,
+                                                                 uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
+                                                                 uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+
 /* Half-precision LLRs to the f32 decoders: what a caller whose soft values exist only as IEEE binary16 (f16) or
  * bfloat16 (bf16) -- a learned demapper's tensors, frames kept in 2 bytes per LLR -- passes instead of an f32 copy.  Both formats
  * travel as their raw bits, `const uint16_t *`.  The library's one widening rule, widen(h), an f32:

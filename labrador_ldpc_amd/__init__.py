@@ -135,6 +135,13 @@ SYMBOLS = {
                                                                             _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
     **{f"labrador_ldpc_decode_ms_cascade_quantised_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _int,
                                                                        _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]) for t in ("i8", "i16")},
+    # f32 LLRs through the bit-sliced i8 kernels' own loader, and the i8 cascade on it
+    "labrador_ldpc_decode_ms_bitsliced_quantised_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int, _optp]),
+    "labrador_ldpc_decode_ms_bitsliced_quantised_corrected_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int,
+                                                                              _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]),
+    "labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _int,
+                                                                            _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
+                                                                            _c.c_uint32, _optp]),
     # f16 / bf16 LLRs, as raw bits, to the f32 decoders
     **{f"labrador_ldpc_widen_llrs_batch_{t}": (_int, [_int, _vp, _vp, _sz, _optp]) for t in ("f16", "bf16")},
     **{f"labrador_ldpc_decode_ms_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f16", "bf16")},
@@ -951,15 +958,35 @@ class LDPCCode(enum.IntEnum):
         return out
 
     def decode_ms_quantised_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, maxiters: int = 50, output=None,
-                                  iters=None, success=None, variant: int = 0, stream: Optional[int] = None, devices=None):
+                                  iters=None, success=None, variant: int = 0, stream: Optional[int] = None, devices=None,
+                                  bitsliced: bool = False, scale_num: Optional[int] = None, scale_shift: Optional[int] = None,
+                                  offset: Optional[int] = None):
         """Decode float32 `llrs[batch, n]` through the integer flooding kernels of `dtype` ("i8", "i16") in one call
         (labrador_ldpc_decode_ms_quantised_batch_i8 / _i16): per frame exactly decode_ms_batch on quantise_llrs_batch(llrs, dtype,
         scale, lim), at kernel `variant`.  Buffers, `stream` and `devices` as decode_ms_batch; host rows cross the link as float32
-        and are quantised on the device.  Returns (output, iters, success)."""
+        and are quantised on the device.  Returns (output, iters, success).
+
+        `bitsliced=True`: the bit-sliced i8 kernels read the float32 rows themselves and quantise in their loader
+        (labrador_ldpc_decode_ms_bitsliced_quantised_batch_i8) -- the same results bit for bit, in one launch without
+        a quantised copy of the batch; TM1536, TM2048, TM6144 and TM8192, `dtype` "i8" and `variant` 0 only.  With it `scale_num`,
+        `scale_shift` and `offset` give the normalized / offset check messages of decode_ms_corrected_batch
+        (labrador_ldpc_decode_ms_bitsliced_quantised_corrected_batch_i8)."""
         np_dtype = _quantised_dtype(dtype)
         if (_is_torch(llrs) or isinstance(llrs, np.ndarray)) and _suffix_or_none(llrs) != "f32":
             raise ValueError("llrs must be float32")
         lim = int(np.iinfo(np_dtype).max) if lim is None else operator.index(lim)
+        triple = _fixed_correction(scale_num, scale_shift, offset)
+        if not bitsliced:
+            if triple is not None:
+                raise ValueError("scale_num, scale_shift and offset need bitsliced=True")
+        else:
+            if dtype != "i8":
+                raise ValueError(f"bitsliced=True decodes dtype i8 only, not {dtype}")
+            if variant != 0:
+                raise ValueError("bitsliced=True has kernel variant 0 only")
+            name = "labrador_ldpc_decode_ms_bitsliced_quantised_" + ("batch_i8" if triple is None else "corrected_batch_i8")
+            return self._batch_call(None, llrs, maxiters, output, iters, success, 0, stream, devices,
+                                    extra=(float(scale), lim, *(triple or ())), fn_name=name)
         return self._batch_call(None, llrs, maxiters, output, iters, success, variant, stream, devices, extra=(float(scale), lim),
                                 fn_name="labrador_ldpc_decode_ms_quantised_batch_" + dtype)
 
@@ -1003,7 +1030,7 @@ class LDPCCode(enum.IntEnum):
                                           variant: int = 0, stream: Optional[int] = None, devices=None, scale_num: Optional[int] = None,
                                           scale_shift: Optional[int] = None, offset: Optional[int] = None,
                                           flooding_scale_num: Optional[int] = None, flooding_scale_shift: Optional[int] = None,
-                                          flooding_offset: Optional[int] = None):
+                                          flooding_offset: Optional[int] = None, bitsliced: bool = False):
         """Decode float32 `llrs[batch, n]` through the integer cascade of `dtype` ("i8", "i16") in one call
         (labrador_ldpc_decode_ms_cascade_quantised_batch_i8 / _i16): per frame exactly decode_ms_cascade_fixed_batch
         -- flooding at cap `maxiters` and kernel `variant`, then the fixed-point layered decoder at cap `max_sweeps` (None =
@@ -1012,8 +1039,21 @@ class LDPCCode(enum.IntEnum):
         capture.  Returns (output, iters, success, stage).
 
         `flooding_scale_num`, `flooding_scale_shift`, `flooding_offset`: the first stage's triple, as decode_ms_cascade_fixed_batch
-        has it (labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8): `dtype` "i8" only."""
+        has it (labrador_ldpc_decode_ms_cascade_quantised_corrected_batch_i8): `dtype` "i8" only.
+
+        `bitsliced=True`: both stages read float32 rows and quantise in their loaders
+        (labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_i8) -- the same four results bit for bit without a
+        quantised copy of the batch; TM1536, TM2048, TM6144 and TM8192, `dtype` "i8" and `variant` 0 only."""
         flooding = _fixed_correction(flooding_scale_num, flooding_scale_shift, flooding_offset)
+        if bitsliced:
+            if dtype != "i8":
+                raise ValueError(f"bitsliced=True decodes dtype i8 only, not {dtype}")
+            if variant != 0:
+                raise ValueError("bitsliced=True has kernel variant 0 only")
+            return self._quantised_call("labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_", llrs, dtype, scale, lim,
+                                        (scale_num, scale_shift, offset), maxiters, output, iters, success, 0, stream, devices,
+                                        caps=(maxiters if max_sweeps is None else max_sweeps,), flooding=flooding or (1, 0, 0), stage=stage,
+                                        with_stage=True)
         if flooding is not None:
             if dtype != "i8":
                 _quantised_dtype(dtype)

@@ -939,23 +939,71 @@ BS_FN void gather_planes(B &b, typename B::V p0, int stage, typename B::V (&X)[8
 // Global side: two 16-byte loads per lane, consecutive lanes consecutive bytes (the wave reads the column's 128-byte lines whole,
 // once).  The loads are unconditional (a predicated load is an EXEC-masked branch per load): lanes of codewords beyond the batch read
 // the group's FIRST frame, which exists, and the value is masked.
+//
+// THE SOURCE (SRC).  RawI8: the rows are the i8 LLRs themselves, as above.  QuantisedF32: the rows are f32 and the
+// loader quantises them by the library's one rule (llr_quantise.hpp, B::quantise4_i8) at (scale, lim) on their way into the slab: per
+// block column the wave reads 8 KB instead of 2 KB, in the shape of llr_quantise.hip -- 16 bytes per lane, consecutive lanes
+// consecutive 16-byte pieces (a wave instruction reads 1 KB of whole lines: 256 LLRs of one codeword, M >= 256 in every code that is
+// built), non-temporal, the four loads of a half-column in flight before the first convert -- and every load's four bytes go to their
+// slab position with one dword store.  The slab then holds what the i8 source would have put there; nothing behind it knows.
+struct RawI8 { using T = int8_t; };
+struct QuantisedF32 { using T = float; float scale, lim; };
+
+// the f32 source's half of load_column_planes: block column c of the group's f32 rows, quantised, into the skewed slab
 template <int CODE, class B, class D>
-BS_FN void load_column_planes(B &b, const D &d, const int8_t *llrs, int c, uint32_t group, uint32_t batch, int stage, typename B::V (&X)[8])
+BS_FN void stage_column_quantised(B &b, const D &d, const float *llrs, int c, uint32_t group, uint32_t batch, int stage, QuantisedF32 source)
+{
+    using GEO = Geo<CODE>;
+    using V = typename B::V;
+    constexpr int M = GEO::M, N = GEO::N, G = GEO::G;
+    // (byte offsets relative to the group's first frame: at most G rows of 4 N bytes)
+    static_assert((uint64_t)G * N * sizeof(float) <= 0xFFFFFFFFull, "the f32 loader's lane offsets fit 32 bits");
+    // (the eight positions of a column are formed from an opaque copy of the lane index: as invariants of the loop over the groups they
+    // were hoisted out of it and held through the iterations -- four more spilled registers on TM2048)
+    V lane = d.lane;
+    B::pin(lane);
+    sfor<0, 2>([&](auto H_) {
+        constexpr int h = decltype(H_)::value;
+        V w[4][4], ok[4];
+        auto pos = [&](int j) { return B::add(B::shl(lane, 2), B::c(256 * (4 * h + j))); };       // slab position of the lane's 4 LLRs
+        sfor<0, 4>([&](auto J_) {
+            constexpr int j = decltype(J_)::value;
+            const V p = pos(j);
+            const V pcw = B::shr(p, ilog2c(M));                                           // their codeword inside the group
+            ok[j] = B::less_u(B::add(B::c(group * (uint32_t)G), pcw), B::c(batch));
+            const V src = B::add(B::mul_u(B::and_(pcw, ok[j]), (uint32_t)N * 4u), B::shl(B::add(B::c((uint32_t)c * M), B::and_(p, B::c(M - 1))), 2));
+            b.gload128(llrs, src, w[j]);
+        });
+        B::fence();                                                                       // (all four loads are out before the first convert)
+        sfor<0, 4>([&](auto J_) {
+            constexpr int j = decltype(J_)::value;
+            const V p = pos(j);
+            const V q4 = B::and_(B::quantise4_i8(w[j], source.scale, source.lim), ok[j]);
+            b.lds_write32(B::add(B::add(p, B::shl(B::shr(p, 8), 4)), B::c(stage)), q4);  // stage_skew(p)
+        });
+    });
+}
+
+template <int CODE, class B, class D, class SRC = RawI8>
+BS_FN void load_column_planes(B &b, const D &d, const typename SRC::T *llrs, int c, uint32_t group, uint32_t batch, int stage, typename B::V (&X)[8],
+                              SRC source = {})
 {
     using GEO = Geo<CODE>;
     using V = typename B::V;
     constexpr int M = GEO::M, N = GEO::N, Q = GEO::Q, W = GEO::W, G = GEO::G;
-    sfor<0, 2>([&](auto H_) {
-        constexpr int h = decltype(H_)::value;
-        const V p = B::add(B::shl(d.lane, 4), B::c(1024 * h));                               // slab position of the lane's 16 bytes
-        const V pcw = B::shr(p, ilog2c(M));                                                   // their codeword inside the group
-        const V ok = B::less_u(B::add(B::c(group * (uint32_t)G), pcw), B::c(batch));
-        const V src = B::add(B::mul_u(B::and_(pcw, ok), (uint32_t)N), B::add(B::c((uint32_t)c * M), B::and_(p, B::c(M - 1))));
-        V w[4];
-        b.gload128(llrs, src, w);
-        sfor<0, 4>([&](auto I_) { constexpr int i = decltype(I_)::value; w[i] = B::and_(w[i], ok); });
-        b.lds_write128(B::add(B::add(p, B::shl(B::shr(p, 8), 4)), B::c(stage)), w);          // stage_skew(p)
-    });
+    if constexpr (std::is_same_v<SRC, QuantisedF32>) stage_column_quantised<CODE>(b, d, llrs, c, group, batch, stage, source);
+    else
+        sfor<0, 2>([&](auto H_) {
+            constexpr int h = decltype(H_)::value;
+            const V p = B::add(B::shl(d.lane, 4), B::c(1024 * h));                               // slab position of the lane's 16 bytes
+            const V pcw = B::shr(p, ilog2c(M));                                                   // their codeword inside the group
+            const V ok = B::less_u(B::add(B::c(group * (uint32_t)G), pcw), B::c(batch));
+            const V src = B::add(B::mul_u(B::and_(pcw, ok), (uint32_t)N), B::add(B::c((uint32_t)c * M), B::and_(p, B::c(M - 1))));
+            V w[4];
+            b.gload128(llrs, src, w);
+            sfor<0, 4>([&](auto I_) { constexpr int i = decltype(I_)::value; w[i] = B::and_(w[i], ok); });
+            b.lds_write128(B::add(B::add(p, B::shl(B::shr(p, 8), 4)), B::c(stage)), w);          // stage_skew(p)
+        });
     // lane (cw, q, ll) gathers the bytes of its 32 indices: q * Q + ll + L * bit; dword dd holds bits dd, 8 + dd, 16 + dd, 24 + dd
     const V cw = B::shr(d.lane, ilog2c(W));
     const V p0 = B::add(B::add(B::shl(cw, ilog2c(M)), B::shl(d.q, ilog2c(Q))), d.ll);       // position of bit 0
@@ -1115,10 +1163,11 @@ BS_FN void init_kernel(B &b)
 // llrs [batch][N] i8, output [batch][NP/8] MSB first, iters [batch], success [batch]; `group` = index of the group of G frames.
 // (Lane offsets are relative to the group's first frame, so they fit 32 bits whatever the batch.)
 // SOFT: app [batch][NP] i8 receives every frame's marginals as well (store_marginals).
-template <int CODE, class B, bool CORRECTED = false, int MULBITS = 8, bool SOFT = false>
-BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint32_t *iters_all, uint8_t *success_all, uint32_t batch,
+// SRC: what the rows of llrs are (load_column_planes): i8, or f32 [batch][N] that the loader quantises at `source`.
+template <int CODE, class B, bool CORRECTED = false, int MULBITS = 8, bool SOFT = false, class SRC = RawI8>
+BS_FN void decode_group(B &b, const typename SRC::T *llrs_all, uint8_t *output_all, uint32_t *iters_all, uint8_t *success_all, uint32_t batch,
                         uint32_t maxiters, uint32_t group, uint32_t scale_num = 1, uint32_t scale_shift = 0, uint32_t offset = 0,
-                        int8_t *app_all = nullptr)
+                        int8_t *app_all = nullptr, SRC source = {})
 {
     using GEO = Geo<CODE>;
     using V = typename B::V;
@@ -1128,7 +1177,7 @@ BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint3
     d.init_lane(b);
     const V lane = d.lane;
     const V cw = B::shr(lane, ilog2c(W));                                    // codeword of the lane inside the group (0 for W = 64)
-    const int8_t *llrs = llrs_all + (size_t)group * G * GEO::N;
+    const typename SRC::T *llrs = llrs_all + (size_t)group * G * GEO::N;
     uint8_t *output = output_all + (size_t)group * G * GEO::OUT_LEN;
     uint32_t *iters = iters_all + (size_t)group * G;
     uint8_t *success = success_all + (size_t)group * G;
@@ -1139,7 +1188,7 @@ BS_FN void decode_group(B &b, const int8_t *llrs_all, uint8_t *output_all, uint3
     sfor<0, NTX>([&](auto C_) {
         constexpr int c = decltype(C_)::value;
         V X[8];
-        load_column_planes<CODE>(b, d, llrs, c, group, batch, GEO::LDS_STAGE, X);
+        load_column_planes<CODE, B, decltype(d), SRC>(b, d, llrs, c, group, batch, GEO::LDS_STAGE, X, source);
         sfor<0, 8>([&](auto K_) {
             constexpr int k = decltype(K_)::value;
             b.lds_write32(B::add(B::shl(lane, 2), B::c(GEO::LDS_LLR + (c * LLRP + k) * 256)), X[k]);

@@ -29,12 +29,7 @@ static_assert(PL == 8, "the corrected form is built for i8 planes");
 // MULBITS: the multiplier bits the form is built for (Decoder::correct_mag): 0 = the offset alone, 4, 8; the launcher picks the form
 // from the call's scale (correction_mulbits).  Three kernels per code.  The rate of the 8-bit form -- any scale with more than four
 // fractional bits -- has not been measured.
-// Waves per SIMD a form is compiled for: the plan's -- but for the rate-1/2 codes' forms with a multiply, which at the plan's three
-// (168 registers) carry 13 to 20 scratch instructions inside the iteration where the plain kernels carry none: those are built for two
-// (DESIGN.md 4.14).
-template <int CODE, int MULBITS>
-constexpr int corrected_waves_per_simd() { return BsPlan<CODE>::RATE == Rate::R12 && MULBITS > 0 ? 2 : BsPlan<CODE>::WAVES_PER_SIMD; }
-
+// Waves per SIMD a form is compiled for: corrected_waves_per_simd() (decode_ms_bs_plan.hpp).
 template <int CODE, int MULBITS>
 __global__ void __launch_bounds__(64, (corrected_waves_per_simd<CODE, MULBITS>()))
 decode_ms_bsc_kernel(const int8_t *__restrict__ llrs, uint8_t *__restrict__ output, uint32_t *__restrict__ iters,

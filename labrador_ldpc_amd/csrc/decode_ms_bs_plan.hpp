@@ -109,6 +109,12 @@ struct BsPlan {
     static constexpr int MIN_GROUPS = (CODE == TM8192 || CODE == TM1280) ? 1024 : (CODE == TM6144 || CODE == TM5120) ? 768 : 2048;
 };
 
+// Waves per SIMD a corrected form (decode_ms_bs_corrected.hip, decode_ms_bs_quantised.hip) is compiled for: the plan's -- but for the
+// rate-1/2 codes' forms with a multiply, which at the plan's three (168 registers) carry 13 to 20 scratch instructions inside the
+// iteration where the plain kernels carry none: those are built for two.
+template <int CODE, int MULBITS>
+constexpr int corrected_waves_per_simd() { return BsPlan<CODE>::RATE == Rate::R12 && MULBITS > 0 ? 2 : BsPlan<CODE>::WAVES_PER_SIMD; }
+
 // ---- the plan as the dispatch reads it at run time: one row per code (the TC codes' rows: no bit-sliced kernel, at any batch size) ----
 struct BsDispatch {
     bool built = false, two_waves = false, refill = false;

@@ -47,6 +47,17 @@ hipError_t launch_decode_ms_bitsliced_corrected_soft(int code, const int8_t *llr
                                                      uint8_t *success, size_t batch, uint32_t maxiters, uint32_t scale_num,
                                                      uint32_t scale_shift, uint32_t offset, hipStream_t stream);
 
+// The bit-sliced i8 flooding kernels of the one-wave TM codes reading f32 LLRs (decode_ms_bs_quantised.hip): the loader
+// quantises every LLR to i8 by the rule of llr_quantise.hpp at (scale, lim), already range-checked; per frame the three results are
+// those of the i8 kernel -- plain, or corrected at the caller's triple -- on the frame quantised that way.  Lockstep kernels at every
+// batch size; llrs 16-byte, output 4-byte aligned (the caller checks).  hipErrorInvalidConfiguration for any other code
+// (bs::bitsliced_soft_code) and in a 16-plane experiment build.
+hipError_t launch_decode_ms_bitsliced_quantised(int code, const float *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
+                                                uint32_t maxiters, float scale, int lim, hipStream_t stream);
+hipError_t launch_decode_ms_bitsliced_quantised_corrected(int code, const float *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
+                                                          size_t batch, uint32_t maxiters, float scale, int lim, uint32_t scale_num,
+                                                          uint32_t scale_shift, uint32_t offset, hipStream_t stream);
+
 // The flooding schedule on f32 LLRs with normalized / offset check messages (decode_ms_flooding_corrected_f32.hip):
 // the code's default f32 kernel with the correction step; scale and offset are the caller's, already range-checked (capi.hip).
 // app == nullptr launches the hard form.  `variant` 0 only: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).

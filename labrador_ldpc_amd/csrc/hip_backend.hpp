@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "llr_quantise.hpp"
+
 #ifndef BS_FN
 #define BS_FN __device__ __forceinline__
 #endif
@@ -76,6 +78,13 @@ struct HipBackend {
         typedef uint32_t u4 __attribute__((ext_vector_type(4), aligned(4)));
         const u4 v = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(static_cast<const char *>(p) + off));
         w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+    // four f32 LLRs (their bits, as gload128 delivers them) -> one dword of four i8 bytes, the first LLR in the low byte, by the
+    // library's one quantisation rule (ldpc::quantise_llr, llr_quantise.hpp): the f32 source of the bit-sliced loader
+    static BS_FN V quantise4_i8(const V (&w)[4], float scale, float lim)
+    {
+        auto q = [&](V bits) { return (V)(uint8_t)quantise_llr<int8_t>(__builtin_bit_cast(float, bits), scale, lim); };
+        return q(w[0]) | q(w[1]) << 8 | q(w[2]) << 16 | q(w[3]) << 24;
     }
     BS_FN void lds_write128(V addr, const V (&w)[4])                    // 16-byte aligned
     {

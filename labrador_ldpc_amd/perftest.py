@@ -31,6 +31,10 @@ included on the cascade) give the i8 flooding decoder -- the whole decode, which
 first stage -- normalized / offset check messages in integers (labrador_ldpc_decode_ms_corrected_batch_i8 /
 labrador_ldpc_decode_ms_cascade_corrected_batch_i8 / _cascade_quantised_corrected_batch_i8, DESIGN.md 4.14: the bit-sliced kernels of
 the TM codes); NUM/DEN and the offset as `--fixed-scale` / `--fixed-offset`; anywhere else they are a ValueError.
+`--bitsliced-loader` (with `--from-f32 --llr i8` and `--schedule flooding` or `cascade`) decodes the f32 frames through the bit-sliced
+kernels' own loader (labrador_ldpc_decode_ms_bitsliced_quantised_batch_i8 / _corrected_batch_i8 /
+labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_i8, DESIGN.md 4.19: TM1536, TM2048, TM6144, TM8192); on the flooding schedule
+it is the only `--from-f32` decode, with or without `--fixed-flooding-scale` / `--fixed-flooding-offset`.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -60,7 +64,7 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
               scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31,
               scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None, from_f32: bool = False,
               flooding_scale: float = 1.0, flooding_offset: float = 0.0, flooding_scale_num=None, flooding_scale_shift=None,
-              flooding_fixed_offset=None):
+              flooding_fixed_offset=None, bitsliced_loader: bool = False):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
     min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
@@ -76,9 +80,13 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     flooding schedule and the cascade's first stage, f32 LLRs only; the defaults are plain min-sum).  `flooding_scale_num`,
     `flooding_scale_shift`, `flooding_fixed_offset`: the i8 flooding decoder's integer correction (decode_ms_corrected_fixed_batch's
     triple; `llr` "i8" on the flooding schedule -- the only i8 flooding decode here -- and as the cascade's first stage, `from_f32`
-    included there; None, the default, is none)."""
+    included there; None, the default, is none).  `bitsliced_loader` (`from_f32`, `llr` "i8", flooding or cascade): the f32 frames go
+    through decode_ms_quantised_batch / decode_ms_cascade_quantised_batch with bitsliced=True -- on the flooding schedule with the
+    flooding triple, if one is given."""
+    if bitsliced_loader and not (from_f32 and llr == "i8" and schedule in ("flooding", "cascade")):
+        raise ValueError("bitsliced_loader belongs to from_f32 with i8 LLRs on the flooding schedule and the cascade")
     fixed_flooding = not (flooding_scale_num is None and flooding_scale_shift is None and flooding_fixed_offset is None)
-    if fixed_flooding and (llr != "i8" or schedule == "layered" or (from_f32 and schedule != "cascade")):
+    if fixed_flooding and (llr != "i8" or schedule == "layered" or (from_f32 and schedule != "cascade" and not bitsliced_loader)):
         raise ValueError("flooding_scale_num, flooding_scale_shift and flooding_fixed_offset belong to i8 LLRs on the flooding schedule "
                          "and the cascade")
     if fixed_flooding and schedule == "flooding" and not (scale_num is None and scale_shift is None and fixed_offset is None):
@@ -91,11 +99,11 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         raise ValueError("max_sweeps belongs to the cascade")
     if llr not in FLOAT_LLRS + ("i8", "i16"):
         raise ValueError(f"unknown LLR type {llr!r}")
-    if llr not in FLOAT_LLRS and ((schedule == "flooding" and not fixed_flooding) or scale != 1.0 or offset != 0.0):
+    if llr not in FLOAT_LLRS and ((schedule == "flooding" and not fixed_flooding and not bitsliced_loader) or scale != 1.0 or offset != 0.0):
         raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
     if llr in FLOAT_LLRS and not (scale_num is None and scale_shift is None and fixed_offset is None):
         raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
-    if from_f32 and (llr in FLOAT_LLRS or schedule == "flooding"):
+    if from_f32 and (llr in FLOAT_LLRS or (schedule == "flooding" and not bitsliced_loader)):
         raise ValueError("from_f32 belongs to the quantised LLRs of the layered schedule and the cascade")
     if (flooding_scale != 1.0 or flooding_offset != 0.0) and (schedule == "layered" or llr != "f32"):
         raise ValueError("flooding_scale and flooding_offset belong to the flooding schedule and the cascade on f32 LLRs")
@@ -118,9 +126,14 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         cw = code.encode_batch(data)                                         # perftest/src/main.rs:10-12
         if from_f32:                                                         # the f32 branch's frames, quantised by the decoder's loader
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds)
-            decode = code.decode_ms_cascade_quantised_batch if schedule == "cascade" else code.decode_ms_layered_quantised_batch
-            out = decode(llrs, llr, llr_scale, llr_lim, maxiters, scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset,
-                         **({"max_sweeps": max_sweeps, **flooding_kw} if schedule == "cascade" else {}))[0]
+            if schedule == "flooding":                                       # (the bit-sliced loader: checked above)
+                triple = dict(zip(("scale_num", "scale_shift", "offset"), flooding_kw.values()))
+                out = code.decode_ms_quantised_batch(llrs, llr, llr_scale, llr_lim, maxiters, bitsliced=True, **triple)[0]
+            else:
+                decode = code.decode_ms_cascade_quantised_batch if schedule == "cascade" else code.decode_ms_layered_quantised_batch
+                out = decode(llrs, llr, llr_scale, llr_lim, maxiters, scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset,
+                             **({"max_sweeps": max_sweeps, **flooding_kw, **({"bitsliced": True} if bitsliced_loader else {})}
+                                if schedule == "cascade" else {}))[0]
         elif llr not in FLOAT_LLRS:                                          # the same noise, quantised by the i8 channel kernel
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
             if schedule == "flooding":                                       # (i8 with a flooding triple: checked above)
@@ -195,15 +208,19 @@ def main(argv=None):
                     help="fixed-point offset min-sum term of the i8 flooding decoder, >= 0 (--llr i8, --schedule flooding / cascade)")
     ap.add_argument("--from-f32", action="store_true",
                     help="generate f32 frames and decode them through the f32-input entries (--llr i8 / i16, --schedule layered / cascade)")
+    ap.add_argument("--bitsliced-loader", action="store_true",
+                    help="decode the f32 frames through the bit-sliced kernels' own loader (--from-f32 --llr i8, --schedule flooding / cascade)")
     args = ap.parse_args(argv)
-    if args.from_f32 and (args.llr in FLOAT_LLRS or args.schedule == "flooding"):
+    if args.bitsliced_loader and not (args.from_f32 and args.llr == "i8" and args.schedule in ("flooding", "cascade")):
+        ap.error("--bitsliced-loader needs --from-f32 --llr i8 and --schedule flooding or cascade")
+    if args.from_f32 and (args.llr in FLOAT_LLRS or (args.schedule == "flooding" and not args.bitsliced_loader)):
         ap.error("--from-f32 needs --llr i8 / i16 and --schedule layered or cascade")
     if args.schedule == "flooding" and (args.scale != 1.0 or args.offset != 0.0):
         ap.error("--scale and --offset need --schedule layered")
     if args.schedule != "cascade" and args.max_sweeps is not None:
         ap.error("--max-sweeps needs --schedule cascade")
     fixed_flooding = args.fixed_flooding_scale is not None or args.fixed_flooding_offset is not None
-    if args.llr not in FLOAT_LLRS and ((args.schedule == "flooding" and not fixed_flooding) or args.scale != 1.0 or args.offset != 0.0):
+    if args.llr not in FLOAT_LLRS and ((args.schedule == "flooding" and not fixed_flooding and not args.bitsliced_loader) or args.scale != 1.0 or args.offset != 0.0):
         ap.error("--llr i8 / i16 needs --schedule layered without --scale and --offset")
     if args.llr in FLOAT_LLRS and (args.fixed_scale is not None or args.fixed_offset is not None):
         ap.error("--fixed-scale and --fixed-offset need --schedule layered --llr i8 / i16")
@@ -220,7 +237,8 @@ def main(argv=None):
                                                   scale_shift=scale_shift, fixed_offset=args.fixed_offset, max_sweeps=args.max_sweeps,
                                                   from_f32=args.from_f32, flooding_scale=args.flooding_scale,
                                                   flooding_offset=args.flooding_offset, flooding_scale_num=fl_num,
-                                                  flooding_scale_shift=fl_shift, flooding_fixed_offset=args.fixed_flooding_offset)
+                                                  flooding_scale_shift=fl_shift, flooding_fixed_offset=args.fixed_flooding_offset,
+                                                  bitsliced_loader=args.bitsliced_loader)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 
