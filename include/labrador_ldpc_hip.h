@@ -363,7 +363,8 @@ int labrador_ldpc_decode_ms_soft_batch_f64(enum labrador_ldpc_code code, const d
  * 16-byte aligned (EINVAL); the input is always copied in.  Host buffers are staged with `app` as the fourth output; device sets
  * shard; asynchronous on opts->stream with MEM_DEVICE -- all as labrador_ldpc_decode_ms_soft_batch_i8.
  * The form with normalized / offset check messages is labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8 below.  There is no
- * _multi, single-frame, quantised (f32-in), slot-refill or two-wave form.  Returns a status code. */
+ * _multi, single-frame, slot-refill or two-wave form; on f32 LLRs: labrador_ldpc_decode_ms_bitsliced_quantised_soft_batch_i8.  Returns
+ * a status code. */
 int labrador_ldpc_decode_ms_bitsliced_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int8_t *app, uint8_t *output,
                                                     uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
                                                     const struct labrador_ldpc_hip_opts *opts);
@@ -383,7 +384,8 @@ int labrador_ldpc_decode_ms_bitsliced_soft_batch_i8(enum labrador_ldpc_code code
  * variant and code family (EUNSUPPORTED, with the texts of labrador_ldpc_decode_ms_bitsliced_soft_batch_i8: TM1280 and TM5120 are told
  * that the two-wave kernels have no soft form) -- all before any device work.  With LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` must be
  * 4-byte, `output` 8-byte and `app` 16-byte aligned (EINVAL).  Memory modes, device sets and `stream` as that entry.
- * There is no _multi, single-frame, quantised (f32-in), slot-refill or two-wave form.  Returns a status code. */
+ * There is no _multi, single-frame, slot-refill or two-wave form; on f32 LLRs:
+ * labrador_ldpc_decode_ms_bitsliced_quantised_corrected_soft_batch_i8.  Returns a status code. */
 int labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int8_t *app,
                                                               uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                                                               size_t max_iters, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
@@ -680,8 +682,8 @@ int labrador_ldpc_decode_ms_cascade_soft_batch_i16(enum labrador_ldpc_code code,
  * only (any other is LABRADOR_LDPC_HIP_EUNSUPPORTED before any device work; TM1280 and TM5120 with the text that the two-wave kernels
  * have no soft form), and with LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` 4-byte aligned (EINVAL).  Chunking
  * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and synchronisation as that entry.  The form with a stage-1 triple is
- * labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8 below.  There is no _multi or quantised (f32-in) form.  Returns a
- * status code. */
+ * labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8 below, the one on f32 LLRs
+ * labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8.  There is no _multi form.  Returns a status code. */
 int labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app,
                                                             uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
                                                             size_t batch, size_t max_iters, size_t max_sweeps, uint32_t scale_num,
@@ -698,8 +700,8 @@ int labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8(enum labrador_ldpc_c
  * Checks: both triples where labrador_ldpc_decode_ms_cascade_corrected_batch_i8 checks them, stage 1's first (EINVAL); then TM1536,
  * TM2048, TM6144 and TM8192 and `variant` 0 only, with the texts of the entry above (EUNSUPPORTED) -- all before any device work; with
  * LABRADOR_LDPC_HIP_MEM_DEVICE `llrs` 4-byte, `output` 8-byte and `app` 16-byte aligned (EINVAL).  Chunking
- * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and synchronisation as the entry above.  There is no _multi or quantised (f32-in) form.  Returns a
- * status code. */
+ * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and synchronisation as the entry above.  On f32 LLRs:
+ * labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8.  There is no _multi form.  Returns a status code. */
 int labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8(enum labrador_ldpc_code code, const int8_t *llrs, int32_t *app,
                                                                       uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
                                                                       size_t batch, size_t max_iters, size_t max_sweeps,
@@ -877,7 +879,7 @@ int labrador_ldpc_decode_ms_cascade_quantised_batch_i16(enum labrador_ldpc_code 
  * pointers; a NULL buffer (`stage` included, where the entry has it); opts->variant != 0, a TC code, TM1280 or TM5120 is
  * EUNSUPPORTED; the ranges of the triples, stage 1's first.  With MEM_DEVICE `output` must be 8-byte and `llrs` 16-byte aligned.
  * Host f32 rows go through the one batched call path and cross the link as f32; device sets shard the frames as for every batched
- * entry.  Hard output only.  The older quantised entries keep their two-pass route.  Returns a status code. */
+ * entry.  Hard output only (the soft forms follow).  The older quantised entries keep their two-pass route.  Returns a status code. */
 int labrador_ldpc_decode_ms_bitsliced_quantised_batch_i8(enum labrador_ldpc_code code, const float *llrs, uint8_t *output, uint32_t *iters,
                                                          uint8_t *success, size_t batch, size_t max_iters, float scale, int lim,
                                                          const struct labrador_ldpc_hip_opts *opts);
@@ -891,6 +893,48 @@ int labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_i8(enum labrador_l
                                                                  uint32_t flooding_scale_num, uint32_t flooding_scale_shift,
                                                                  uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
                                                                  uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+
+/* ... WITH SOFT OUTPUT: the three entries above returning every frame's a-posteriori LLRs as well -- what an iterative
+ * demapper or equaliser that holds f32 LLRs calls.  The soft bit-sliced kernels with the quantiser in their loader: no quantised copy
+ * of the batch, no workspace and no chunk loop in the first two, one launch per slice, asynchronous on opts->stream with MEM_DEVICE.
+ * Per frame f, exactly, in `app`, `output`, `iters`, `success` (and `stage`),
+ *     _bitsliced_quantised_soft_batch_i8             labrador_ldpc_decode_ms_bitsliced_soft_batch_i8
+ *     _bitsliced_quantised_corrected_soft_batch_i8   labrador_ldpc_decode_ms_bitsliced_corrected_soft_batch_i8 at (scale_num, scale_shift,
+ *                                                    offset)
+ *     _cascade_bitsliced_quantised_soft_batch_i8     labrador_ldpc_decode_ms_cascade_bitsliced_corrected_soft_batch_i8 at the two triples
+ *                                                    (an identity stage-1 triple: labrador_ldpc_decode_ms_cascade_bitsliced_soft_batch_i8)
+ * on (labrador_ldpc_quantise_llrs_batch_i8 of frame f at (scale, lim)), bit for bit, for every f32 input, +-0, +-inf, NaN (an erasure),
+ * denormals and ties included; the hard results are therefore also those of the three entries above.
+ *   app  flooding: [batch][n + p] int8, the decoder's saturating marginal va, reaching -128; all zero for max_iters = 0; punctured
+ *        variables last.  A converged frame carries va of its converging iteration, any other frame va of the last iteration.
+ *        cascade: [batch][n + p] int32 -- a stage-0 frame carries the flooding marginal sign-extended, a stage-1 frame the layered
+ *        decoder's exact sum (labrador_ldpc_decode_ms_cascade_soft_batch_i8 has the rest); comparable only within a stage.
+ * An identity triple (1 << k, k, 0) runs the plain kernel.  The cascade's stage 1 reads the caller's f32 rows and writes int8 marginals
+ * into the cascade's workspace, widened from there into `app`; the failed frames' f32 rows are gathered
+ * (LABRADOR_LDPC_HIP_CASCADE_CHUNK) and stage 2 is labrador_ldpc_decode_ms_layered_quantised_soft_batch_i8's kernel at the stage-2
+ * triple; like every cascade it SYNCHRONISES opts->stream once per launch slice and must not be called on a stream that is being
+ * captured into a graph.
+ * Lockstep kernels of the four one-wave codes TM1536, TM2048, TM6144 and TM8192 at every batch size, kernel variant 0 only.
+ * Arguments are checked in this order, all before any device work: `code`; `scale` and `lim`; an empty batch is OK whatever the
+ * pointers; a NULL buffer (`app` included, and `stage` where the entry has it); opts->variant != 0, a TC code, TM1280 or TM5120 is
+ * EUNSUPPORTED with a text that names the four codes; the ranges of the triples, stage 1's first.  With MEM_DEVICE `output` must be
+ * 8-byte and `llrs` and `app` 16-byte aligned (EINVAL).  Host f32 rows go through the one batched call path and cross the link as f32,
+ * `app` comes back as a further output; device sets shard the frames as for every batched entry.  There is no _multi, single-frame,
+ * i16, slot-refill or two-wave form.  Returns a status code. */
+int labrador_ldpc_decode_ms_bitsliced_quantised_soft_batch_i8(enum labrador_ldpc_code code, const float *llrs, int8_t *app, uint8_t *output,
+                                                              uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters, float scale,
+                                                              int lim, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_bitsliced_quantised_corrected_soft_batch_i8(enum labrador_ldpc_code code, const float *llrs, int8_t *app,
+                                                                        uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
+                                                                        size_t max_iters, float scale, int lim, uint32_t scale_num,
+                                                                        uint32_t scale_shift, uint32_t offset,
+                                                                        const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8(enum labrador_ldpc_code code, const float *llrs, int32_t *app,
+                                                                      uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
+                                                                      size_t batch, size_t max_iters, size_t max_sweeps, float scale, int lim,
+                                                                      uint32_t flooding_scale_num, uint32_t flooding_scale_shift,
+                                                                      uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
+                                                                      uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
 
 /* Half-precision LLRs to the f32 decoders: what a caller whose soft values exist only as IEEE binary16 (f16) or
  * bfloat16 (bf16) -- a learned demapper's tensors, frames kept in 2 bytes per LLR -- passes instead of an f32 copy.  Both formats

@@ -142,6 +142,13 @@ SYMBOLS = {
     "labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _c.c_float, _int,
                                                                             _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
                                                                             _c.c_uint32, _optp]),
+    # ... with soft output: `app` behind `llrs`
+    "labrador_ldpc_decode_ms_bitsliced_quantised_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int, _optp]),
+    "labrador_ldpc_decode_ms_bitsliced_quantised_corrected_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _c.c_float, _int,
+                                                                                   _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]),
+    "labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz,
+                                                                                 _c.c_float, _int, _c.c_uint32, _c.c_uint32, _c.c_uint32,
+                                                                                 _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]),
     # f16 / bf16 LLRs, as raw bits, to the f32 decoders
     **{f"labrador_ldpc_widen_llrs_batch_{t}": (_int, [_int, _vp, _vp, _sz, _optp]) for t in ("f16", "bf16")},
     **{f"labrador_ldpc_decode_ms_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f16", "bf16")},
@@ -1065,6 +1072,52 @@ class LDPCCode(enum.IntEnum):
         return self._quantised_call("labrador_ldpc_decode_ms_cascade_quantised_batch_", llrs, dtype, scale, lim,
                                     (scale_num, scale_shift, offset), maxiters, output, iters, success, variant, stream, devices,
                                     caps=(maxiters if max_sweeps is None else max_sweeps,), stage=stage, with_stage=True)
+
+    def _bitsliced_quantised_soft_call(self, name, llrs, maxiters, extra, app, app_dtype, output, iters, success, stream, devices, **kw):
+        """the float32-input soft calls on the bit-sliced int8 kernels: `name` is the entry, `extra` what goes
+        behind maxiters; any dtype but float32 has no kernel"""
+        if (_is_torch(llrs) or isinstance(llrs, np.ndarray)) and _suffix_or_none(llrs) != "f32":
+            raise LdpcHipError(f"no batched kernel for dtype {llrs.dtype} (float32 only)")
+        return self._batch_call(None, llrs, maxiters, output, iters, success, 0, stream, devices, soft=True, app=app, app_dtype=app_dtype,
+                                extra=extra, fn_name=name, **kw)
+
+    def decode_ms_bitsliced_quantised_soft_batch(self, llrs, scale: float, lim: int, maxiters: int = 50, app=None, output=None, iters=None,
+                                                 success=None, stream: Optional[int] = None, devices=None,
+                                                 scale_num: Optional[int] = None, scale_shift: Optional[int] = None,
+                                                 offset: Optional[int] = None):
+        """Decode float32 `llrs[batch, n]` on the bit-sliced int8 kernels WITH soft output in one call
+        (labrador_ldpc_decode_ms_bitsliced_quantised_soft_batch_i8): per frame exactly decode_ms_bitsliced_soft_batch on
+        quantise_llrs_batch(llrs, "i8", scale, lim), all four results bit for bit.  The kernel quantises as it loads: no quantised
+        copy of the batch exists, and with device buffers the call is one launch, asynchronous on `stream`.  TM1536, TM2048, TM6144
+        and TM8192 only; float32 numpy arrays or torch tensors only -- any other dtype raises LdpcHipError.  With device buffers
+        `llrs` and `app` must be 16-byte aligned.  Buffers, `stream` and `devices` as decode_ms_batch.
+
+        `scale_num`, `scale_shift`, `offset`: normalized / offset min-sum, the triple as decode_ms_bitsliced_soft_batch takes it
+        (labrador_ldpc_decode_ms_bitsliced_quantised_corrected_soft_batch_i8).  None given: the plain entry.
+        Returns (app[batch, n + p] int8 -- punctured variables last --, output, iters, success)."""
+        triple = _fixed_correction(scale_num, scale_shift, offset)
+        name = "labrador_ldpc_decode_ms_bitsliced_quantised_" + ("soft_batch_i8" if triple is None else "corrected_soft_batch_i8")
+        return self._bitsliced_quantised_soft_call(name, llrs, maxiters, (float(scale), operator.index(lim), *(triple or ())), app, "i8",
+                                                   output, iters, success, stream, devices)
+
+    def decode_ms_cascade_bitsliced_quantised_soft_batch(self, llrs, scale: float, lim: int, maxiters: int = 50,
+                                                         max_sweeps: Optional[int] = None, app=None, output=None, iters=None, success=None,
+                                                         stage=None, stream: Optional[int] = None, devices=None,
+                                                         flooding_scale_num: Optional[int] = None, flooding_scale_shift: Optional[int] = None,
+                                                         flooding_offset: Optional[int] = None, scale_num: Optional[int] = None,
+                                                         scale_shift: Optional[int] = None, offset: Optional[int] = None):
+        """Decode float32 `llrs[batch, n]` through the soft int8 cascade whose first stage is decode_ms_bitsliced_quantised_soft_batch
+        (labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8): per frame exactly
+        decode_ms_cascade_fixed_soft_batch(bitsliced=True) at the same caps and triples on quantise_llrs_batch(llrs, "i8", scale, lim),
+        all five results bit for bit, without a quantised copy of the batch.  `flooding_*` is the first stage's triple, `scale_num`,
+        `scale_shift` and `offset` the layered stage's; none given: the identity.  `max_sweeps` None = `maxiters`.  Codes, dtypes and
+        alignments as decode_ms_bitsliced_quantised_soft_batch; the call waits on the stream once per launch slice and must not run
+        on a stream under capture.  Returns (app[batch, n + p] int32, output, iters, success, stage)."""
+        extra = (maxiters if max_sweeps is None else max_sweeps, float(scale), operator.index(lim),
+                 *(_fixed_correction(flooding_scale_num, flooding_scale_shift, flooding_offset) or (1, 0, 0)),
+                 *(_fixed_correction(scale_num, scale_shift, offset) or (1, 0, 0)))
+        return self._bitsliced_quantised_soft_call("labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8", llrs, maxiters, extra,
+                                                   app, "i32", output, iters, success, stream, devices, stage=stage, with_stage=True)
 
     # ---- synthetic channel (harness) ----
     def awgn_frames(self, codewords, batch: int, sigma: float, seed: int, dtype="f32",

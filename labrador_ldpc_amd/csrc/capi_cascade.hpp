@@ -98,11 +98,13 @@ thread_local CascadeWorkspace g_cascade;
 // frames, back to back on the stream, each into the workspace's `data` block and widened from there into the caller's int32 rows
 // (never in place: a parallel front-to-back widening overwrites sources not yet read); the workspace is therefore taken before
 // stage 1 then, and `compact` still runs once, over the whole slice.
-template <class T, class A = T, class Stage1, class Stage2>
+// M: the type of stage 1's marginals -- T, but for the cascade whose stage 1 reads f32 rows and quantises in its loader (DESIGN.md
+// 4.20): T = float, M = int8_t, A = int32_t.
+template <class T, class A = T, class M = T, class Stage1, class Stage2>
 hipError_t cascade_slice(const ldpc::CodeInfo &ci, const T *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, uint8_t *stage,
                          size_t nb, hipStream_t stream, const Stage1 &stage1, const Stage2 &stage2, A *app = nullptr)
 {
-    constexpr bool WIDENS = !std::is_same_v<T, A>;
+    constexpr bool WIDENS = !std::is_same_v<M, A>;
     const size_t n = ci.n, np = (size_t)ci.n + ci.p, out_len = ci.output_len();
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     CascadeWorkspace &ws = g_cascade;
@@ -119,20 +121,20 @@ hipError_t cascade_slice(const ldpc::CodeInfo &ci, const T *llrs, uint8_t *outpu
     if constexpr (WIDENS) {
         if (app) {
             if (hipError_t e = take_workspace(); e != hipSuccess) return e;
-            const size_t chunk = std::min(cascade_chunk_frames(np * sizeof(T)), nb);
-            if (hipError_t e = ws.reserve(ws.data, up(chunk * np * sizeof(T))); e != hipSuccess) return e;
-            T *const d_app = static_cast<T *>(ws.data.p);
+            const size_t chunk = std::min(cascade_chunk_frames(np * sizeof(M)), nb);
+            if (hipError_t e = ws.reserve(ws.data, up(chunk * np * sizeof(M))); e != hipSuccess) return e;
+            M *const d_app = static_cast<M *>(ws.data.p);
             for (size_t f0 = 0; f0 < nb; f0 += chunk) {
                 const size_t nf = std::min(chunk, nb - f0);
                 if (hipError_t e = stage1(llrs + f0 * n, d_app, output + f0 * out_len, iters + f0, success + f0, nf, stream); e != hipSuccess)
                     return e;
-                if (hipError_t e = ldpc::launch_cascade_widen_app<T>(d_app, app + f0 * np, nf * np, stream); e != hipSuccess) return e;
+                if (hipError_t e = ldpc::launch_cascade_widen_app<M>(d_app, app + f0 * np, nf * np, stream); e != hipSuccess) return e;
             }
             stage1_done = true;
         }
     }
     if (!stage1_done) {
-        T *app1 = nullptr;
+        M *app1 = nullptr;
         if constexpr (!WIDENS) app1 = app;
         if (hipError_t e = stage1(llrs, app1, output, iters, success, nb, stream); e != hipSuccess) return e;
         if (hipError_t e = take_workspace(); e != hipSuccess) return e;

@@ -58,6 +58,15 @@ hipError_t launch_decode_ms_bitsliced_quantised_corrected(int code, const float 
                                                           size_t batch, uint32_t maxiters, float scale, int lim, uint32_t scale_num,
                                                           uint32_t scale_shift, uint32_t offset, hipStream_t stream);
 
+// ... with soft output as well (decode_ms_bs_quantised_soft.hip): the four results are those of
+// launch_decode_ms_bitsliced_soft / launch_decode_ms_bitsliced_corrected_soft on the frame quantised that way, app [batch][n + p] i8
+// 16-byte aligned.
+hipError_t launch_decode_ms_bitsliced_quantised_soft(int code, const float *llrs, int8_t *app, uint8_t *output, uint32_t *iters,
+                                                     uint8_t *success, size_t batch, uint32_t maxiters, float scale, int lim, hipStream_t stream);
+hipError_t launch_decode_ms_bitsliced_quantised_corrected_soft(int code, const float *llrs, int8_t *app, uint8_t *output, uint32_t *iters,
+                                                               uint8_t *success, size_t batch, uint32_t maxiters, float scale, int lim,
+                                                               uint32_t scale_num, uint32_t scale_shift, uint32_t offset, hipStream_t stream);
+
 // The flooding schedule on f32 LLRs with normalized / offset check messages (decode_ms_flooding_corrected_f32.hip):
 // the code's default f32 kernel with the correction step; scale and offset are the caller's, already range-checked (capi.hip).
 // app == nullptr launches the hard form.  `variant` 0 only: anything else is hipErrorInvalidConfiguration (EUNSUPPORTED).
