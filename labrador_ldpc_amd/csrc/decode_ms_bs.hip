@@ -15,12 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#ifndef BS_TU
-#error "decode_ms_bs.hip is compiled per unit: -DBS_TU=1 (rate 1/2 + dispatch) or -DBS_TU=2 (rate 2/3, rate 4/5)"
-#endif
-
 #include "decode_ms_bitslice.hpp"
 #include "decode_ms_bitslice_split.hpp"
+#include "decode_ms_bs_launch.hpp"
 #include "hip_backend.hpp"
 #include "occupancy.hpp"
 
@@ -133,20 +130,7 @@ decode_ms_bs_split_refill_kernel(const int8_t *__restrict__ llrs, uint8_t *__res
     else split_wave_refill<CODE, 1>(lds, ticket_word, llrs, output, iters, success, batch, maxiters, queue, chunk);
 }
 
-// ---- the two launchers, each for the one-wave (BLOCK 64) and the two-wave (BLOCK 128) form of its kernel ----
-// lockstep: one group of G codewords per workgroup, the hardware dispatcher hands them out
-template <auto KERNEL, int BLOCK, int G>
-hipError_t launch_lockstep(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream)
-{
-    if (batch == 0) return hipSuccess;
-    if (batch > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const size_t groups = (batch + G - 1) / G;
-    const size_t grid = groups < 0x7FFFFFFFull ? groups : 0x7FFFFFFFull;
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(BLOCK), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters, (uint32_t)groups);
-    return hipGetLastError();
-}
-
-// slot refill: the resident workgroups draw chunks of frames from the launch's queue word
+// ---- slot refill: the resident workgroups draw chunks of frames from the launch's queue word
 template <auto KERNEL, int BLOCK, int G, int ROUNDS>
 hipError_t launch_refill(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream,
                          uint32_t *queue)
@@ -165,65 +149,46 @@ hipError_t launch_refill(const int8_t *llrs, uint8_t *output, uint32_t *iters, u
 
 uint32_t *bs_queue_word(hipStream_t stream);          // decode_ms_i8.hip: the launch queue's word of (device, stream), or nullptr (claim_counter)
 
-// A code's kernel as its plan says: one wave or two per group; with `refill`, where the build carries the slot-refill form and the
-// stream has a queue word (all but a stream under capture), that form -- 8 rounds of slots per draw, 4 on the two-wave kernel
-template <int CODE>
-hipError_t launch_code(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters, hipStream_t stream, int refill)
-{
-    using PLAN = BsPlan<CODE>;
-    constexpr int G = PLAN::G;
-    if constexpr (PLAN::REFILL) {
-        if (uint32_t *queue = refill ? bs_queue_word(stream) : nullptr) {
-            if constexpr (PLAN::TWO_WAVES) return launch_refill<decode_ms_bs_split_refill_kernel<CODE>, 128, G, 4>(llrs, output, iters, success, batch, maxiters, stream, queue);
-            else return launch_refill<decode_ms_bs_refill_kernel<CODE>, 64, G, 8>(llrs, output, iters, success, batch, maxiters, stream, queue);
-        }
-    }
-    if constexpr (PLAN::TWO_WAVES) return launch_lockstep<decode_ms_bs_split_kernel<CODE>, 128, G>(llrs, output, iters, success, batch, maxiters, stream);
-    else return launch_lockstep<decode_ms_bs_kernel<CODE>, 64, G>(llrs, output, iters, success, batch, maxiters, stream);
-}
-
-// the codes THIS compile unit builds (BsPlan::UNIT); hipErrorInvalidConfiguration for every other code
-static hipError_t launch_in_unit(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters,
-                          hipStream_t stream, int refill)
-{
-    auto built_here = [&](auto C_) {
-        constexpr int CODE = decltype(C_)::value;
-        if constexpr (BsPlan<CODE>::UNIT == BS_TU) return launch_code<CODE>(llrs, output, iters, success, batch, maxiters, stream, refill);
-        else return hipErrorInvalidConfiguration;
+// The plain form (decode_ms_bs_launch.hpp): a code's kernel as its plan says, one wave or two per group; with `refill`, where the build
+// carries the slot-refill form and the stream has a queue word (all but a stream under capture), that form -- 8 rounds of slots per
+// draw, 4 on the two-wave kernel.  Its text compiles with 16 planes as well.
+struct PlainForm {
+    static constexpr bool I8_ONLY = false;
+    struct Args {
+        const int8_t *llrs; uint8_t *output; uint32_t *iters; uint8_t *success; size_t batch; uint32_t maxiters; hipStream_t stream; int refill;
     };
-    switch (code) {
-        case TM1280: return built_here(IC<TM1280>{});
-        case TM1536: return built_here(IC<TM1536>{});
-        case TM2048: return built_here(IC<TM2048>{});
-        case TM5120: return built_here(IC<TM5120>{});
-        case TM6144: return built_here(IC<TM6144>{});
-        case TM8192: return built_here(IC<TM8192>{});
-        default: return hipErrorInvalidConfiguration;
+    using Codes = TmCodes;
+    template <int CODE>
+    static hipError_t launch(const Args &a)
+    {
+        using PLAN = BsPlan<CODE>;
+        constexpr int G = PLAN::G;
+        if constexpr (PLAN::REFILL) {
+            if (uint32_t *queue = a.refill ? bs_queue_word(a.stream) : nullptr) {
+                if constexpr (PLAN::TWO_WAVES)
+                    return launch_refill<decode_ms_bs_split_refill_kernel<CODE>, 128, G, 4>(a.llrs, a.output, a.iters, a.success, a.batch, a.maxiters, a.stream, queue);
+                else return launch_refill<decode_ms_bs_refill_kernel<CODE>, 64, G, 8>(a.llrs, a.output, a.iters, a.success, a.batch, a.maxiters, a.stream, queue);
+            }
+        }
+        const std::tuple lead{a.llrs, a.output, a.iters, a.success};
+        if constexpr (PLAN::TWO_WAVES) return launch_lockstep<decode_ms_bs_split_kernel<CODE>, 128, G>(a.stream, a.batch, a.maxiters, lead);
+        else return launch_lockstep<decode_ms_bs_kernel<CODE>, 64, G>(a.stream, a.batch, a.maxiters, lead);
     }
-}
+};
 
 }  // namespace bs
 
+#if BS_TU == 2
+template hipError_t bs::launch_in_unit2<bs::PlainForm>(int, const bs::PlainForm::Args &);
+#else
 // i8 LLRs through the bit-sliced kernel; hipErrorInvalidConfiguration for the codes it is not built for (the TC codes: their
 // circulants are not quarter-wise rotations).  llrs 4-byte aligned, output 4-byte aligned (the caller checks).
 // refill: 1 = slot refill where the code has it (BsPlan::REFILL), 0 = the lockstep kernels
-hipError_t launch_decode_ms_bitsliced_unit2(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
-                                            uint32_t maxiters, hipStream_t stream, int refill);
-#if BS_TU == 2
-hipError_t launch_decode_ms_bitsliced_unit2(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
-                                            uint32_t maxiters, hipStream_t stream, int refill)
-{
-    return bs::launch_in_unit(code, llrs, output, iters, success, batch, maxiters, stream, refill);
-}
-#else
+// (a 16-plane experiment build, tools/bs_alt_build.sh -DBS_PLANES=16, carries the rate-1/2 codes only: launch_form)
 hipError_t launch_decode_ms_bitsliced(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                                       uint32_t maxiters, hipStream_t stream, int refill)
 {
-    if (!bs::bitsliced_code(code)) return hipErrorInvalidConfiguration;
-    if (bs::BS_DISPATCH[code].unit == BS_TU) return bs::launch_in_unit(code, llrs, output, iters, success, batch, maxiters, stream, refill);
-    // (a 16-plane experiment build, tools/bs_alt_build.sh -DBS_PLANES=16, carries the rate-1/2 codes only)
-    if constexpr (bs::PL != 8) return hipErrorInvalidConfiguration;
-    else return launch_decode_ms_bitsliced_unit2(code, llrs, output, iters, success, batch, maxiters, stream, refill);
+    return bs::launch_form<bs::PlainForm>(code, {llrs, output, iters, success, batch, maxiters, stream, refill});
 }
 #endif
 

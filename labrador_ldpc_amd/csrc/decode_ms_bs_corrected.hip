@@ -12,19 +12,14 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#ifndef BS_TU
-#error "decode_ms_bs_corrected.hip is compiled per unit: -DBS_TU=1 (rate 1/2 + dispatch) or -DBS_TU=2 (rate 2/3, rate 4/5)"
-#endif
-
 #include "decode_ms_bitslice.hpp"
 #include "decode_ms_bitslice_split.hpp"
+#include "decode_ms_bs_launch.hpp"
 #include "decode_ms_protos.hpp"
 #include "hip_backend.hpp"
 
 namespace ldpc {
 namespace bs {
-
-static_assert(PL == 8, "the corrected form is built for i8 planes");
 
 // MULBITS: the multiplier bits the form is built for (Decoder::correct_mag): 0 = the offset alone, 4, 8; the launcher picks the form
 // from the call's scale (correction_mulbits).  Three kernels per code.  The rate of the 8-bit form -- any scale with more than four
@@ -69,74 +64,38 @@ decode_ms_bsc_split_kernel(const int8_t *__restrict__ llrs, uint8_t *__restrict_
         split_wave_corrected<CODE, 1, MULBITS>(lds, llrs, output, iters, success, batch, maxiters, ngroups, scale_num, scale_shift, offset);
 }
 
-// one group of G codewords per workgroup, the hardware dispatcher hands them out (launch_lockstep of decode_ms_bs.hip)
-template <auto KERNEL, int BLOCK, int G>
-hipError_t launch_lockstep_corrected(const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters,
-                                     uint32_t scale_num, uint32_t scale_shift, uint32_t offset, hipStream_t stream)
-{
-    if (batch == 0) return hipSuccess;
-    if (batch > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const size_t groups = (batch + G - 1) / G;
-    const size_t grid = groups < 0x7FFFFFFFull ? groups : 0x7FFFFFFFull;
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(BLOCK), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters, (uint32_t)groups,
-                       scale_num, scale_shift, offset);
-    return hipGetLastError();
-}
-
-// the codes THIS compile unit builds (BsPlan::UNIT); hipErrorInvalidConfiguration for every other code
-static hipError_t launch_corrected_in_unit(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
-                                           uint32_t maxiters, uint32_t scale_num, uint32_t scale_shift, uint32_t offset, hipStream_t stream)
-{
-    auto form = [&](auto C_, auto M_) {
-        constexpr int CODE = decltype(C_)::value, MULBITS = decltype(M_)::value;
+// The corrected form (decode_ms_bs_launch.hpp): one wave or two per group as the code's plan says, in the width the call's scale needs
+struct CorrectedForm {
+    static constexpr bool I8_ONLY = true;
+    struct Args {
+        const int8_t *llrs; uint8_t *output; uint32_t *iters; uint8_t *success; size_t batch; uint32_t maxiters;
+        uint32_t scale_num, scale_shift, offset; hipStream_t stream;
+    };
+    using Codes = TmCodes;
+    template <int CODE>
+    static hipError_t launch(const Args &a)
+    {
         using PLAN = BsPlan<CODE>;
-        if constexpr (PLAN::UNIT != BS_TU) return hipErrorInvalidConfiguration;
-        else if constexpr (PLAN::TWO_WAVES)
-            return launch_lockstep_corrected<decode_ms_bsc_split_kernel<CODE, MULBITS>, 128, PLAN::G>(llrs, output, iters, success, batch, maxiters,
-                                                                                                       scale_num, scale_shift, offset, stream);
-        else
-            return launch_lockstep_corrected<decode_ms_bsc_kernel<CODE, MULBITS>, 64, PLAN::G>(llrs, output, iters, success, batch, maxiters,
-                                                                                                scale_num, scale_shift, offset, stream);
-    };
-    auto built_here = [&](auto C_) {
-        switch (correction_mulbits(scale_num, scale_shift)) {
-            case 0: return form(C_, IC<0>{});
-            case 4: return form(C_, IC<4>{});
-            default: return form(C_, IC<8>{});
-        }
-    };
-    switch (code) {
-        case TM1280: return built_here(IC<TM1280>{});
-        case TM1536: return built_here(IC<TM1536>{});
-        case TM2048: return built_here(IC<TM2048>{});
-        case TM5120: return built_here(IC<TM5120>{});
-        case TM6144: return built_here(IC<TM6144>{});
-        case TM8192: return built_here(IC<TM8192>{});
-        default: return hipErrorInvalidConfiguration;
+        return for_mulbits(a.scale_num, a.scale_shift, [&](auto M_) {
+            constexpr int MULBITS = decltype(M_)::value;
+            const std::tuple lead{a.llrs, a.output, a.iters, a.success};
+            if constexpr (PLAN::TWO_WAVES)
+                return launch_lockstep<decode_ms_bsc_split_kernel<CODE, MULBITS>, 128, PLAN::G>(a.stream, a.batch, a.maxiters, lead, a.scale_num, a.scale_shift, a.offset);
+            else return launch_lockstep<decode_ms_bsc_kernel<CODE, MULBITS>, 64, PLAN::G>(a.stream, a.batch, a.maxiters, lead, a.scale_num, a.scale_shift, a.offset);
+        });
     }
-}
+};
 
 }  // namespace bs
 
-hipError_t launch_decode_ms_bitsliced_corrected_unit2(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
-                                                      size_t batch, uint32_t maxiters, uint32_t scale_num, uint32_t scale_shift,
-                                                      uint32_t offset, hipStream_t stream);
 #if BS_TU == 2
-hipError_t launch_decode_ms_bitsliced_corrected_unit2(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success,
-                                                      size_t batch, uint32_t maxiters, uint32_t scale_num, uint32_t scale_shift,
-                                                      uint32_t offset, hipStream_t stream)
-{
-    return bs::launch_corrected_in_unit(code, llrs, output, iters, success, batch, maxiters, scale_num, scale_shift, offset, stream);
-}
+template hipError_t bs::launch_in_unit2<bs::CorrectedForm>(int, const bs::CorrectedForm::Args &);
 #else
 hipError_t launch_decode_ms_bitsliced_corrected(int code, const int8_t *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
                                                 uint32_t maxiters, uint32_t scale_num, uint32_t scale_shift, uint32_t offset,
                                                 hipStream_t stream)
 {
-    if (!bs::bitsliced_code(code)) return hipErrorInvalidConfiguration;
-    if (bs::BS_DISPATCH[code].unit == BS_TU)
-        return bs::launch_corrected_in_unit(code, llrs, output, iters, success, batch, maxiters, scale_num, scale_shift, offset, stream);
-    return launch_decode_ms_bitsliced_corrected_unit2(code, llrs, output, iters, success, batch, maxiters, scale_num, scale_shift, offset, stream);
+    return bs::launch_form<bs::CorrectedForm>(code, {llrs, output, iters, success, batch, maxiters, scale_num, scale_shift, offset, stream});
 }
 #endif
 

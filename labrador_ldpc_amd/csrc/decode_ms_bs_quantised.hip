@@ -14,11 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#ifndef BS_TU
-#error "decode_ms_bs_quantised.hip is compiled per unit: -DBS_TU=1 (rate 1/2 + dispatch) or -DBS_TU=2 (rate 2/3)"
-#endif
-
 #include "decode_ms_bitslice.hpp"
+#include "decode_ms_bs_launch.hpp"
 #include "decode_ms_protos.hpp"
 #include "hip_backend.hpp"
 
@@ -55,85 +52,42 @@ decode_ms_bsqc_kernel(const float *__restrict__ llrs, uint8_t *__restrict__ outp
                                                                            offset, nullptr, QuantisedF32{scale, lim});
 }
 
-// one group of G codewords per workgroup, the hardware dispatcher hands them out (launch_lockstep of decode_ms_bs.hip)
-template <auto KERNEL, int G, class... Extra>
-hipError_t launch_lockstep_quantised(const float *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters,
-                                     hipStream_t stream, Extra... extra)
-{
-    if (batch == 0) return hipSuccess;
-    if (batch > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    const size_t groups = (batch + G - 1) / G;
-    const size_t grid = groups < 0x7FFFFFFFull ? groups : 0x7FFFFFFFull;
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(64), 0, stream, llrs, output, iters, success, (uint32_t)batch, maxiters, (uint32_t)groups,
-                       extra...);
-    return hipGetLastError();
-}
-
-// the codes THIS compile unit builds (BsPlan::UNIT); hipErrorInvalidConfiguration for every other code.  `corrected` chooses the form
-// with the correction step, in the width the call's scale needs (correction_mulbits); else the triple is not read.
-static hipError_t launch_quantised_in_unit(int code, const float *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
-                                           uint32_t maxiters, float scale, float lim, bool corrected, uint32_t scale_num, uint32_t scale_shift,
-                                           uint32_t offset, hipStream_t stream)
-{
-    auto form = [&](auto C_, auto M_) {
-        constexpr int CODE = decltype(C_)::value, MULBITS = decltype(M_)::value;
-        return launch_lockstep_quantised<decode_ms_bsqc_kernel<CODE, MULBITS>, BsPlan<CODE>::G>(llrs, output, iters, success, batch, maxiters, stream,
-                                                                                                 scale, lim, scale_num, scale_shift, offset);
+// The f32-reading form (decode_ms_bs_launch.hpp): the one-wave codes.  `corrected` chooses the kernel with the correction step, in the
+// width the call's scale needs; else the triple is not read.
+struct QuantisedForm {
+    static constexpr bool I8_ONLY = true;
+    struct Args {
+        const float *llrs; uint8_t *output; uint32_t *iters; uint8_t *success; size_t batch; uint32_t maxiters; float scale, lim;
+        bool corrected; uint32_t scale_num, scale_shift, offset; hipStream_t stream;
     };
-    auto built_here = [&](auto C_) {
-        constexpr int CODE = decltype(C_)::value;
-        if constexpr (BsPlan<CODE>::UNIT != BS_TU) return hipErrorInvalidConfiguration;
-        else {
-            if (!corrected)
-                return launch_lockstep_quantised<decode_ms_bsq_kernel<CODE>, BsPlan<CODE>::G>(llrs, output, iters, success, batch, maxiters, stream,
-                                                                                              scale, lim);
-            switch (correction_mulbits(scale_num, scale_shift)) {
-                case 0: return form(C_, IC<0>{});
-                case 4: return form(C_, IC<4>{});
-                default: return form(C_, IC<8>{});
-            }
-        }
-    };
-    switch (code) {
-        case TM1536: return built_here(IC<TM1536>{});
-        case TM2048: return built_here(IC<TM2048>{});
-        case TM6144: return built_here(IC<TM6144>{});
-        case TM8192: return built_here(IC<TM8192>{});
-        default: return hipErrorInvalidConfiguration;
+    using Codes = OneWaveCodes;
+    template <int CODE>
+    static hipError_t launch(const Args &a)
+    {
+        constexpr int G = BsPlan<CODE>::G;
+        const std::tuple lead{a.llrs, a.output, a.iters, a.success};
+        if (!a.corrected) return launch_lockstep<decode_ms_bsq_kernel<CODE>, 64, G>(a.stream, a.batch, a.maxiters, lead, a.scale, a.lim);
+        return for_mulbits(a.scale_num, a.scale_shift, [&](auto M_) {
+            return launch_lockstep<decode_ms_bsqc_kernel<CODE, decltype(M_)::value>, 64, G>(a.stream, a.batch, a.maxiters, lead, a.scale, a.lim, a.scale_num,
+                                                                                            a.scale_shift, a.offset);
+        });
     }
-}
+};
 
 }  // namespace bs
 #endif
 
-hipError_t launch_decode_ms_bitsliced_quantised_unit2(int code, const float *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
-                                                      uint32_t maxiters, float scale, float lim, bool corrected, uint32_t scale_num,
-                                                      uint32_t scale_shift, uint32_t offset, hipStream_t stream);
 #if BS_TU == 2
-hipError_t launch_decode_ms_bitsliced_quantised_unit2(int code, const float *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
-                                                      uint32_t maxiters, float scale, float lim, bool corrected, uint32_t scale_num,
-                                                      uint32_t scale_shift, uint32_t offset, hipStream_t stream)
-{
 #if BS_PLANES == 8
-    return bs::launch_quantised_in_unit(code, llrs, output, iters, success, batch, maxiters, scale, lim, corrected, scale_num, scale_shift, offset,
-                                        stream);
-#else
-    return hipErrorInvalidConfiguration;
+template hipError_t bs::launch_in_unit2<bs::QuantisedForm>(int, const bs::QuantisedForm::Args &);
 #endif
-}
 #else
 namespace {
 hipError_t launch_quantised(int code, const float *llrs, uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, uint32_t maxiters,
                             float scale, float lim, bool corrected, uint32_t scale_num, uint32_t scale_shift, uint32_t offset, hipStream_t stream)
 {
 #if BS_PLANES == 8
-    // (the one-wave lockstep codes: the soft form's four)
-    if (!bs::bitsliced_soft_code(code)) return hipErrorInvalidConfiguration;
-    if (bs::BS_DISPATCH[code].unit == BS_TU)
-        return bs::launch_quantised_in_unit(code, llrs, output, iters, success, batch, maxiters, scale, lim, corrected, scale_num, scale_shift,
-                                            offset, stream);
-    return launch_decode_ms_bitsliced_quantised_unit2(code, llrs, output, iters, success, batch, maxiters, scale, lim, corrected, scale_num,
-                                                      scale_shift, offset, stream);
+    return bs::launch_form<bs::QuantisedForm>(code, {llrs, output, iters, success, batch, maxiters, scale, lim, corrected, scale_num, scale_shift, offset, stream});
 #else
     return hipErrorInvalidConfiguration;                       // (a 16-plane experiment build carries no f32 loader)
 #endif

@@ -5,17 +5,15 @@ with the formula, exhaustively, and (b) the whole decoder -- the one-wave form o
 form of TM1280 and TM5120, each in the form the launcher picks for the triple -- with tests/flooding_fixed_corrected_restatement.py.
 The GPU tests then only have to show that gfx950 executes the same text the same way (tests/test_gpu_bs_corrected.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import edge_frames
+import bitslice_emu_build
 import oracle
 import flooding_fixed_corrected_restatement as fr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TM = ["TM1280", "TM1536", "TM2048", "TM5120", "TM6144", "TM8192"]
 TRIPLES = [(1, 0, 0), (13, 4, 0), (1, 0, 1), (3, 2, 1), (1, 1, 0), (255, 8, 0), (1, 8, 0), (16, 4, 127)]
 CAPS = (0, 1, 3, 25)
@@ -25,21 +23,9 @@ OFFSETS = (0, 1, 2, 63, 127)
 @pytest.fixture(scope="module")
 def emu():
     """One shared object per code, the stale ones rebuilt in parallel (fully unrolled 64-lane code, three forms: ~1/2 minute each)."""
-    csrc = os.path.join(ROOT, "labrador_ldpc_amd", "csrc")
-    src = [os.path.join(ROOT, "tests", "c", "bitslice_corrected_emu.cpp")] + \
-          [os.path.join(csrc, f) for f in ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "codes.hpp", "decode_ms_bs_plan.hpp",
-                                           "decode_ms_tuning.hpp")]
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    libs, jobs = {}, []
-    for name in TM:
-        lib = os.path.join(ROOT, "build", f"libbitslice_corrected_emu_{name}.so")
-        libs[name] = lib
-        if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in src):
-            jobs.append(subprocess.Popen(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", f"-DEMU_CODE={name}", "-I" + csrc, src[0], "-o", lib]))
-    assert all(j.wait() == 0 for j in jobs)
+    libs = bitslice_emu_build.build("bitslice_corrected_emu.cpp", ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "codes.hpp", "decode_ms_bs_plan.hpp", "decode_ms_tuning.hpp"), TM)
     loaded = {}
-    for name, lib in libs.items():
-        L = ctypes.CDLL(lib)
+    for name, L in libs.items():
         L.bsc_emu_decode.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t] + [ctypes.c_uint32] * 4
         L.bsc_emu_correct.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
         assert L.bsc_emu_code() == oracle.CODES.index(name)

@@ -6,16 +6,14 @@ and the hard results with the statement (tests/flooding_fixed_corrected_soft_res
 kept planes is built -- the soft plan's, for every form -- so one is emulated.  The GPU tests then only have to show that gfx950
 executes the same text the same way (tests/test_gpu_bs_corrected_soft.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bs_corrected_soft_frames as bcf
+import bitslice_emu_build
 import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TM = bcf.NAMES
 # every triple in the form the launcher picks, and (13,4,0) in the 8-bit form as well
 FORMS = [(t, bcf.mulbits(t)) for t in bcf.TRIPLES] + [((13, 4, 0), 8)]
@@ -24,21 +22,9 @@ FORMS = [(t, bcf.mulbits(t)) for t in bcf.TRIPLES] + [((13, 4, 0), 8)]
 @pytest.fixture(scope="module")
 def emu():
     """One shared object per code, the stale ones rebuilt in parallel (fully unrolled 64-lane code, three forms: ~1/2 minute each)."""
-    csrc = os.path.join(ROOT, "labrador_ldpc_amd", "csrc")
-    src = [os.path.join(ROOT, "tests", "c", "bitslice_corrected_soft_emu.cpp")] + \
-          [os.path.join(csrc, f) for f in ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "codes.hpp", "decode_ms_bs_plan.hpp",
-                                           "decode_ms_tuning.hpp")]
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    libs, jobs = {}, []
-    for name in TM:
-        lib = os.path.join(ROOT, "build", f"libbitslice_corrected_soft_emu_{name}.so")
-        libs[name] = lib
-        if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in src):
-            jobs.append(subprocess.Popen(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", f"-DEMU_CODE={name}", "-I" + csrc, src[0], "-o", lib]))
-    assert all(j.wait() == 0 for j in jobs)
+    libs = bitslice_emu_build.build("bitslice_corrected_soft_emu.cpp", ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "codes.hpp", "decode_ms_bs_plan.hpp", "decode_ms_tuning.hpp"), TM)
     loaded = {}
-    for name, lib in libs.items():
-        L = ctypes.CDLL(lib)
+    for name, L in libs.items():
         L.bsca_emu_decode.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_uint32] * 4 + [ctypes.c_int]
         L.bsca_emu_mulbits.argtypes = [ctypes.c_uint32] * 2
         assert L.bsca_emu_code() == oracle.CODES.index(name)

@@ -9,37 +9,26 @@ text the same way (tests/test_gpu_bitslice.py)."""
 import ctypes
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import bitslice_emu_build
 import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TM = ["TM1280", "TM1536", "TM2048", "TM5120", "TM6144", "TM8192"]
+EMU_DEPS = ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "decode_bf_bitslice.hpp", "codes.hpp", "decode_ms_bs_plan.hpp",
+            "decode_ms_tuning.hpp")
 
 
 @pytest.fixture(scope="module")
 def emu():
     """decode(code, llrs, maxiters) through the emulated kernel; one shared object per code, the stale ones rebuilt in parallel
     (fully unrolled 64-lane code: ~1 minute each at -O1)."""
-    src = [os.path.join(ROOT, "tests", "c", "bitslice_emu.cpp"), os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_bitslice.hpp"),
-           os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_bitslice_split.hpp"), os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_bf_bitslice.hpp"),
-           os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "codes.hpp"), os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_bs_plan.hpp"),
-           os.path.join(ROOT, "labrador_ldpc_amd", "csrc", "decode_ms_tuning.hpp")]
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    libs, jobs = {}, []
-    for name in TM:
-        lib = os.path.join(ROOT, "build", f"libbitslice_emu_{name}.so")
-        libs[name] = lib
-        if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in src):
-            jobs.append(subprocess.Popen(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", f"-DEMU_CODE={name}",
-                                          "-I" + os.path.join(ROOT, "labrador_ldpc_amd", "csrc"), src[0], "-o", lib]))
-    assert all(j.wait() == 0 for j in jobs)
+    libs = bitslice_emu_build.build("bitslice_emu.cpp", EMU_DEPS, TM)
     loaded = {}
-    for name, lib in libs.items():
-        L = ctypes.CDLL(lib)
+    for name, L in libs.items():
         L.bs_emu_decode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
         L.bs_emu_decode_bf.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
         L.bs_emu_decode_split.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
@@ -168,14 +157,8 @@ def test_sixteen_plane_build_equals_the_i16_oracle(name):
     sums of six +-127 messages), where the 8-plane build saturates and the 16-plane one must not.  (The GPU rate of this build:
     profiles/r05_kbench/bs_i16_tc.txt.)"""
     code = oracle.CODES.index(name)
-    lib = os.path.join(ROOT, "build", f"libbitslice_emu16_{name}.so")
-    src = [os.path.join(ROOT, "tests", "c", "bitslice_emu.cpp")] + [os.path.join(ROOT, "labrador_ldpc_amd", "csrc", f) for f in
-           ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "decode_bf_bitslice.hpp", "codes.hpp", "decode_ms_bs_plan.hpp",
-            "decode_ms_tuning.hpp")]
-    if not os.path.exists(lib) or any(os.path.getmtime(f) > os.path.getmtime(lib) for f in src):
-        subprocess.check_call(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", f"-DEMU_CODE={name}", "-DBS_PLANES=16", "-DLDPC_TUNING_OVERRIDES_ALLOWED",
-                               "-I" + os.path.join(ROOT, "labrador_ldpc_amd", "csrc"), src[0], "-o", lib])
-    L = ctypes.CDLL(lib)
+    L = bitslice_emu_build.build("bitslice_emu.cpp", EMU_DEPS, [name],
+                                 variants={"planes16": lambda name: ["-DBS_PLANES=16", "-DLDPC_TUNING_OVERRIDES_ALLOWED"]})[(name, "planes16")]
     L.bs_emu_decode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
     rng = np.random.default_rng(1600 + code)
     differs_from_i8 = False

@@ -10,17 +10,18 @@ behind every result array, `app` included.  The GPU tests then only have to show
 (tests/test_gpu_bs_quantised_soft.py)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bs_quantised_soft_frames as bqs
+import bitslice_emu_build
 import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TM = bqs.NAMES
 ROCM_INC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
+# (the library's flags for the one multiply: nothing fused into it; the HIP headers llr_quantise.hpp needs)
+F32_FLAGS = ["-fno-fast-math", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC]
 # the corrected form: every triple in the form the launcher picks -- (13,4,0) four bits, (1,0,1) the offset alone, (200,8,1) eight
 FORMS = [(t, bqs.mulbits(t)) for t in bqs.TRIPLES]
 assert [m for _, m in FORMS] == [4, 0, 8]
@@ -29,23 +30,9 @@ assert [m for _, m in FORMS] == [4, 0, 8]
 @pytest.fixture(scope="module")
 def emu():
     """One shared object per code, the stale ones rebuilt in parallel (fully unrolled 64-lane code, eight forms: a minute or two each)."""
-    csrc = os.path.join(ROOT, "labrador_ldpc_amd", "csrc")
-    src = [os.path.join(ROOT, "tests", "c", "bitslice_quantised_soft_emu.cpp")] + \
-          [os.path.join(csrc, f) for f in ("decode_ms_bitslice.hpp", "codes.hpp", "decode_ms_bs_plan.hpp", "decode_ms_tuning.hpp",
-                                           "llr_quantise.hpp")]
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    libs, jobs = {}, []
-    for name in TM:
-        lib = os.path.join(ROOT, "build", f"libbitslice_quantised_soft_emu_{name}.so")
-        libs[name] = lib
-        if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in src):
-            # (the library's flags for the one multiply: nothing fused into it)
-            jobs.append(subprocess.Popen(["g++", "-O1", "-std=c++20", "-fno-fast-math", "-ffp-contract=off", "-shared", "-fPIC",
-                                          f"-DEMU_CODE={name}", "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INC, "-I" + csrc, src[0], "-o", lib]))
-    assert all(j.wait() == 0 for j in jobs)
+    libs = bitslice_emu_build.build("bitslice_quantised_soft_emu.cpp", ("decode_ms_bitslice.hpp", "codes.hpp", "decode_ms_bs_plan.hpp", "decode_ms_tuning.hpp", "llr_quantise.hpp"), TM, F32_FLAGS)
     loaded = {}
-    for name, lib in libs.items():
-        L = ctypes.CDLL(lib)
+    for name, L in libs.items():
         L.bsqa_emu_decode.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float, ctypes.c_float] + \
                                      [ctypes.c_uint32] * 3 + [ctypes.c_int]
         L.bsqa_emu_decode_i8.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t] + [ctypes.c_uint32] * 4 + [ctypes.c_int]

@@ -5,16 +5,14 @@ and this file compares the marginals and the hard results with the oracle frame 
 emulated for every code: the plan's (what the library ships) and the other one (what tools/bs_soft_rate.py measures against it).  The
 GPU tests then only have to show that gfx950 executes the same text the same way (tests/test_gpu_bs_soft.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bs_soft_frames as bsf
+import bitslice_emu_build
 import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TM = bsf.NAMES
 CAPS = bsf.CAPS
 PLACEMENTS = ("plan", "other")
@@ -29,24 +27,10 @@ def other_placement_flags(name):
 @pytest.fixture(scope="module")
 def emu():
     """One shared object per code and placement, the stale ones rebuilt in parallel (fully unrolled 64-lane code: ~1/2 minute each)."""
-    csrc = os.path.join(ROOT, "labrador_ldpc_amd", "csrc")
-    src = [os.path.join(ROOT, "tests", "c", "bitslice_soft_emu.cpp")] + \
-          [os.path.join(csrc, f) for f in ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "codes.hpp", "decode_ms_bs_plan.hpp",
-                                           "decode_ms_tuning.hpp")]
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    libs, jobs = {}, []
-    for name in TM:
-        for placement in PLACEMENTS:
-            lib = os.path.join(ROOT, "build", f"libbitslice_soft_emu_{name}_{placement}.so")
-            libs[(name, placement)] = lib
-            if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in src):
-                extra = other_placement_flags(name) if placement == "other" else []
-                jobs.append(subprocess.Popen(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", f"-DEMU_CODE={name}", "-I" + csrc] + extra +
-                                             [src[0], "-o", lib]))
-    assert all(j.wait() == 0 for j in jobs)
+    libs = bitslice_emu_build.build("bitslice_soft_emu.cpp", ("decode_ms_bitslice.hpp", "decode_ms_bitslice_split.hpp", "codes.hpp", "decode_ms_bs_plan.hpp", "decode_ms_tuning.hpp"), TM,
+                                    variants={"plan": lambda name: [], "other": other_placement_flags})
     loaded = {}
-    for (name, placement), lib in libs.items():
-        L = ctypes.CDLL(lib)
+    for (name, placement), L in libs.items():
         L.bsa_emu_decode.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_uint32]
         L.bsa_emu_decode_plain.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_uint32]
         assert L.bsa_emu_code() == oracle.CODES.index(name)
