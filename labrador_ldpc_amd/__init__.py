@@ -834,9 +834,12 @@ class LDPCCode(enum.IntEnum):
             raise LdpcHipError(err)
         return bool(ok), int(iters.value)
 
-    def decode_bf_batch(self, input, maxiters: int = 50, stream: Optional[int] = None, devices=None):
+    def decode_bf_batch(self, input, maxiters: int = 50, stream: Optional[int] = None, devices=None, output=None, iters=None,
+                        success=None):
         """input[batch, n/8] -> (output[batch, output_len], iters[batch], success[batch]).
-        numpy = host buffers, torch CUDA uint8 tensors = device buffers (asynchronous)."""
+        numpy = host buffers, torch CUDA uint8 tensors = device buffers (asynchronous).  `output`, `iters`, `success`: the caller's
+        result buffers, as decode_ms_batch takes them (None = new ones); with all three given the call allocates nothing, which is
+        what a stream under graph capture needs."""
         if input.ndim != 2 or input.shape[1] != self.n() // 8:
             raise ValueError("input must be [batch, n/8]")
         batch = input.shape[0]
@@ -848,9 +851,9 @@ class LDPCCode(enum.IntEnum):
         else:
             input = np.ascontiguousarray(input, dtype=np.uint8)
             opts, _keep = _host_opts(stream, 0, devices)
-        output = _result_buffer(None, input, (batch, self.output_len()), "u8", "output")
-        iters = _result_buffer(None, input, (batch,), "i32", "iters")
-        success = _result_buffer(None, input, (batch,), "u8", "success")
+        output = _result_buffer(output, input, (batch, self.output_len()), "u8", "output")
+        iters = _result_buffer(iters, input, (batch,), "i32", "iters")
+        success = _result_buffer(success, input, (batch,), "u8", "success")
         _check(lib.labrador_ldpc_decode_bf_batch(int(self), _ptr(input), _ptr(output), _ptr(iters), _ptr(success),
                                                  batch, maxiters, ctypes.byref(opts)))
         return output, iters, success
