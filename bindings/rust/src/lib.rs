@@ -177,6 +177,8 @@ extern "C" {
     pub fn labrador_ldpc_decode_ms_bitsliced_quantised_soft_batch_i8(code: LDPCCode, llrs: *const f32, app: *mut i8, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_bitsliced_quantised_corrected_soft_batch_i8(code: LDPCCode, llrs: *const f32, app: *mut i8, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8(code: LDPCCode, llrs: *const f32, app: *mut i32, output: *mut u8, iters: *mut u32, success: *mut u8, stage: *mut u8, batch: usize, max_iters: usize, max_sweeps: usize, scale: f32, lim: c_int, flooding_scale_num: u32, flooding_scale_shift: u32, flooding_offset: u32, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_bitsliced_hard_batch_i8(code: LDPCCode, input: *const u8, erasures: *const u8, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, magnitude: c_int, opts: *const HipOpts) -> c_int;
+    pub fn labrador_ldpc_decode_ms_bitsliced_hard_corrected_batch_i8(code: LDPCCode, input: *const u8, erasures: *const u8, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, magnitude: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_quantised_batch_i8(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_quantised_batch_i16(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, opts: *const HipOpts) -> c_int;
     pub fn labrador_ldpc_decode_ms_layered_quantised_batch_i8(code: LDPCCode, llrs: *const f32, output: *mut u8, iters: *mut u32, success: *mut u8, batch: usize, max_iters: usize, scale: f32, lim: c_int, scale_num: u32, scale_shift: u32, offset: u32, opts: *const HipOpts) -> c_int;

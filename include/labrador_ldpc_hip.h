@@ -936,6 +936,37 @@ int labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8(enum labra
                                                                       uint32_t flooding_offset, uint32_t scale_num, uint32_t scale_shift,
                                                                       uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
 
+/* PACKED HARD DECISIONS through the bit-sliced i8 flooding kernels' OWN LOADER: what a hard-decision receiver calls
+ * instead of labrador_ldpc_hard_to_llrs_batch_i8 into a buffer of n bytes per frame followed by labrador_ldpc_decode_ms_batch_i8.  A
+ * packed frame already is the kernels' sign plane, so there is no expanded copy of the batch, no workspace and no chunk loop -- one
+ * launch per slice, and with MEM_DEVICE the call is asynchronous on opts->stream with nothing to wait for and may be captured into a
+ * graph.
+ *   input     [batch][n / 8]  packed bits, MSB first, as labrador_ldpc_decode_bf_batch and labrador_ldpc_hard_to_llrs_batch_* take them
+ *   erasures  NULL, or [batch][n / 8] in the same packing: a set bit marks a position the receiver knows to be bad
+ *   magnitude 1 .. 127: the confidence every unerased position goes in with.  At 1 -- the reference's hard_to_llrs -- the integer
+ *             correction is a no-op ((13 * 1 + 8) >> 4 == 1); at 127 the saturating sums clip at once.
+ * Per frame f, exactly,
+ *     _bitsliced_hard_batch_i8             labrador_ldpc_decode_ms_batch_i8
+ *     _bitsliced_hard_corrected_batch_i8   labrador_ldpc_decode_ms_corrected_batch_i8 at (scale_num, scale_shift, offset)
+ * on the i8 frame e, e[j] = 0 if bit j of `erasures` is set, else -magnitude if bit j of `input` is set, else +magnitude, at cap
+ * max_iters: output, iters and success are that entry's, bit for bit.  With magnitude 1 and no mask e is
+ * labrador_ldpc_hard_to_llrs_batch_i8's frame.  An identity triple (1 << k, k, 0) runs the plain kernel.
+ * Lockstep kernels of the four one-wave codes TM1536, TM2048, TM6144 and TM8192 at every batch size, kernel variant 0 only.
+ * Arguments are checked in this order, all before any device work: `code`; `magnitude` (EINVAL, with the value in the text); an empty
+ * batch is OK whatever the pointers; a NULL `input`, `output`, `iters` or `success` (`erasures` may be NULL); opts->variant != 0, a TC
+ * code, TM1280 or TM5120 is EUNSUPPORTED with a text that names the four codes; the ranges of the triple.  With MEM_DEVICE `output`
+ * must be 8-byte and `input` and `erasures` 4-byte aligned (EINVAL): the loader reads one dword per lane.  Host rows go through the one
+ * batched call path and cross the link packed, n / 8 bytes per frame and twice that with a mask; device sets shard the frames as for
+ * every batched entry.  There is no _multi, single-frame, i16, soft-output, cascade, slot-refill or two-wave form.  Returns a status
+ * code. */
+int labrador_ldpc_decode_ms_bitsliced_hard_batch_i8(enum labrador_ldpc_code code, const uint8_t *input, const uint8_t *erasures,
+                                                    uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch, size_t max_iters,
+                                                    int magnitude, const struct labrador_ldpc_hip_opts *opts);
+int labrador_ldpc_decode_ms_bitsliced_hard_corrected_batch_i8(enum labrador_ldpc_code code, const uint8_t *input, const uint8_t *erasures,
+                                                              uint8_t *output, uint32_t *iters, uint8_t *success, size_t batch,
+                                                              size_t max_iters, int magnitude, uint32_t scale_num, uint32_t scale_shift,
+                                                              uint32_t offset, const struct labrador_ldpc_hip_opts *opts);
+
 /* Half-precision LLRs to the f32 decoders: what a caller whose soft values exist only as IEEE binary16 (f16) or
  * bfloat16 (bf16) -- a learned demapper's tensors, frames kept in 2 bytes per LLR -- passes instead of an f32 copy.  Both formats
  * travel as their raw bits, `const uint16_t *`.  The library's one widening rule, widen(h), an f32:

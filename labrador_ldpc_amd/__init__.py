@@ -149,6 +149,11 @@ SYMBOLS = {
     "labrador_ldpc_decode_ms_cascade_bitsliced_quantised_soft_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz,
                                                                                  _c.c_float, _int, _c.c_uint32, _c.c_uint32, _c.c_uint32,
                                                                                  _c.c_uint32, _c.c_uint32, _c.c_uint32, _optp]),
+    # packed hard decisions through the bit-sliced i8 kernels' own loader: `erasures` behind `input`, `magnitude` behind max_iters
+    # 
+    "labrador_ldpc_decode_ms_bitsliced_hard_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _int, _optp]),
+    "labrador_ldpc_decode_ms_bitsliced_hard_corrected_batch_i8": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _int, _c.c_uint32,
+                                                                         _c.c_uint32, _c.c_uint32, _optp]),
     # f16 / bf16 LLRs, as raw bits, to the f32 decoders
     **{f"labrador_ldpc_widen_llrs_batch_{t}": (_int, [_int, _vp, _vp, _sz, _optp]) for t in ("f16", "bf16")},
     **{f"labrador_ldpc_decode_ms_batch_{t}": (_int, [_int, _vp, _vp, _vp, _vp, _sz, _sz, _optp]) for t in ("f16", "bf16")},
@@ -914,6 +919,51 @@ class LDPCCode(enum.IntEnum):
         output = _result_buffer(output, llrs, (batch, self.n() // 8), "u8", "output")
         _check(getattr(lib, "labrador_ldpc_llrs_to_hard_batch_" + _suffix(llrs))(int(self), _ptr(llrs), _ptr(output), batch, ctypes.byref(opts)))
         return output
+
+    # ---- packed hard decisions to the bit-sliced i8 min-sum kernels ----
+    def decode_ms_hard_batch(self, input, maxiters: int = 50, magnitude: int = 1, erasures=None, output=None, iters=None, success=None,
+                             stream: Optional[int] = None, devices=None, scale_num: Optional[int] = None,
+                             scale_shift: Optional[int] = None, offset: Optional[int] = None):
+        """Decode packed hard decisions `input[batch, n/8]` (MSB first, as decode_bf_batch takes them) by min-sum on the bit-sliced i8
+        kernels, whose loader reads the packed rows itself (labrador_ldpc_decode_ms_bitsliced_hard_batch_i8): per frame exactly
+        decode_ms_batch on the int8 frame that is 0 where the bit of `erasures[batch, n/8]` is set, else -magnitude where the bit of
+        `input` is set, else +magnitude -- without that frame ever existing.  `magnitude` 1 .. 127 (1 is hard_to_llrs_batch's frame);
+        `erasures` None = no position erased.  `scale_num`, `scale_shift`, `offset`: the normalized / offset check messages of
+        decode_ms_corrected_fixed_batch (labrador_ldpc_decode_ms_bitsliced_hard_corrected_batch_i8); none given: the plain entry.
+        numpy = host buffers, which cross the link packed; torch CUDA uint8 tensors = device buffers (asynchronous on `stream`, 4-byte
+        aligned, may be captured into a graph).  TM1536, TM2048, TM6144 and TM8192.  Returns (output, iters, success)."""
+        if not (_is_torch(input) or isinstance(input, np.ndarray)):
+            raise ValueError("input must be a numpy array (host) or a torch CUDA tensor (device)")
+        if input.ndim != 2 or input.shape[1] != self.n() // 8:
+            raise ValueError("input must be [batch, n/8]")
+        batch = input.shape[0]
+        if erasures is not None:
+            if not (_is_torch(erasures) or isinstance(erasures, np.ndarray)) or _is_torch(erasures) != _is_torch(input) \
+                    or tuple(erasures.shape) != tuple(input.shape):
+                raise ValueError("erasures must be of input's kind and shape")
+        if not _is_torch(input):                         # (packed bits: a cast would change them without a word)
+            for name, a in (("input", input), ("erasures", erasures)):
+                if a is not None and a.dtype != np.uint8:
+                    raise ValueError(f"{name} must be a uint8 array of packed bits, not {a.dtype}")
+        if _is_torch(input):
+            import torch
+            for name, t in (("input", input), ("erasures", erasures)):
+                if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.device == input.device):
+                    raise ValueError(f"{name} must be a contiguous uint8 CUDA tensor" + ("" if t is input else " on input's device"))
+            opts = _device_opts(input, stream)
+        else:
+            input = np.ascontiguousarray(input)
+            if erasures is not None:
+                erasures = np.ascontiguousarray(erasures)
+            opts, _keep = _host_opts(stream, 0, devices)
+        output = _result_buffer(output, input, (batch, self.output_len()), "u8", "output")
+        iters = _result_buffer(iters, input, (batch,), "i32", "iters")
+        success = _result_buffer(success, input, (batch,), "u8", "success")
+        triple = _fixed_correction(scale_num, scale_shift, offset)
+        fn = getattr(lib, "labrador_ldpc_decode_ms_bitsliced_hard_" + ("batch_i8" if triple is None else "corrected_batch_i8"))
+        _check(fn(int(self), _ptr(input), None if erasures is None else _ptr(erasures), _ptr(output), _ptr(iters), _ptr(success), batch,
+                  maxiters, operator.index(magnitude), *(triple or ()), ctypes.byref(opts)))
+        return output, iters, success
 
     # ---- f32 soft values to the integer decoders (DESIGN.md 4.10) ----
     def quantise_llrs_batch(self, llrs, dtype="i8", scale: float = 8.0, lim: Optional[int] = None, out=None, stream: Optional[int] = None):

@@ -43,20 +43,34 @@ struct FixedCorrection {
 // ---- one batched call path ------------------------------------------------------------------------------------------------------
 // The buffers of a batched call: one input and up to five outputs, each an address and its bytes per item.  Item f of a buffer
 // starts f * bytes behind its address -- the only pointer arithmetic of the shard re-entry, the device slices and the staged call.
-// An output that is not there (a hard-only decode's `app`) is NULL and stays NULL.
+// An output that is not there (a hard-only decode's `app`) is NULL and stays NULL; so does the second input, which one entry has
+// (the erasure rows of the packed hard-decision decode).
 struct Buffers {
     const void *in;
     size_t in_bytes;
     HostOut out[5];
+    const void *in2 = nullptr;
+    size_t in2_bytes = 0;
     Buffers from(size_t item) const
     {
         Buffers b = *this;
         b.in = static_cast<const char *>(in) + item * in_bytes;
+        if (in2) b.in2 = static_cast<const char *>(in2) + item * in2_bytes;
         for (HostOut &o : b.out)
             if (o.host) o.host = static_cast<char *>(o.host) + item * o.bytes_per_item;
         return b;
     }
 };
+// a launch that takes the second input takes it behind the first: launch(in, in2, ...), else launch(in, ...).  The form is chosen by
+// what the launch can be called with, so every launch handed to batched_call is a lambda with CONCRETE parameter types: a generic one
+// (auto parameters) would be callable both ways and get `in2` where it expects its outputs.  minsum_call's slice launch takes `in2`
+// for every min-sum entry -- NULL for all but the packed hard-decision ones -- so that the frame stays one function.
+template <class Launch, class... Rest>
+auto launch_with(const Launch &launch, const void *in, const void *in2, Rest... rest)
+{
+    if constexpr (std::is_invocable_v<const Launch &, const void *, const void *, Rest...>) return launch(in, in2, rest...);
+    else return launch(in, rest...);
+}
 
 // What a batched entry does once its own arguments are checked: over a device set, every device's worker runs its share of the
 // items through this function again; device-resident buffers are checked by the entry (device_checks() -> status, the text its own)
@@ -83,16 +97,16 @@ int batched_call(const Buffers &b, size_t batch, const labrador_ldpc_hip_opts *o
             const Buffers slice = b.from(f0);
             void *outs[NOUT];
             for (int o = 0; o < NOUT; ++o) outs[o] = slice.out[o].host;
-            return launch(slice.in, outs, nb, stream);
+            return launch_with(launch, slice.in, slice.in2, (void *const *)outs, nb, stream);
         }));
     }
     if (opts && opts->memory != LABRADOR_LDPC_HIP_MEM_HOST) return fail(LABRADOR_LDPC_HIP_EINVAL, "bad opts->memory");
 
     // host buffers: staged in chunks (arbitrarily large batches fit), copies overlapped with the kernel
     return host_pipeline<NOUT>(b.in, b.in_bytes, b.out, batch, stream,
-                               [&](void *d_in, void *const *d_out, size_t, size_t nb, hipStream_t st) -> int {
-        return status_of(launch(d_in, d_out, nb, st));
-    }, direct_in);
+                               [&](void *d_in, void *d_in2, void *const *d_out, size_t, size_t nb, hipStream_t st) -> int {
+        return status_of(launch_with(launch, (const void *)d_in, (const void *)d_in2, d_out, nb, st));
+    }, direct_in, b.in2, b.in2_bytes);
 }
 
 // status_of of the entries outside min-sum: "<name> launch: <the runtime's text>"
@@ -107,6 +121,7 @@ auto launch_status(const char *name)
 // ---- the call frame of the batched min-sum entries --------------------------------------------------------------------------------
 // The buffers of a min-sum call -- the caller's, and again a launch's share of them, on the device.  `stage` [batch] exists for the
 // cascade entries and `app` [batch][n + p], in elements of A, for the soft ones; an `app` given to an entry without one is ignored.
+// `mask` exists for the packed hard-decision entries, whose rows -- input and mask alike -- are n / 8 bytes (`packed`); it may be NULL.
 template <class In, class A>
 struct MsBuffers {
     const In *llrs;
@@ -116,6 +131,8 @@ struct MsBuffers {
     uint8_t *stage = nullptr;
     A *app = nullptr;
     bool has_stage = false, has_app = false;
+    const In *mask = nullptr;
+    bool packed = false;
 };
 // what a launch runs at: the code, opts->variant, and the caller's caps clamped to the kernels' 32 bits
 struct MsRun {
@@ -125,16 +142,18 @@ struct MsRun {
 // what an entry wants of the device side of a call
 struct MsDevice {
     const char *unsupported;                          // the EUNSUPPORTED text of hipErrorInvalidConfiguration, a format of (variant, code)
-    size_t llrs_align = 0;                            // with MEM_DEVICE `llrs` has this alignment, else EINVAL; 0 asks for nothing
+    size_t llrs_align = 0;                            // with MEM_DEVICE `llrs` (and `mask`) has this alignment, else EINVAL; 0 asks for nothing
     // does the launch read every LLR exactly once?  Then the smallest host calls may let it read them across the link.
     bool (*reads_llrs_once)(int code, int variant) = [](int, int) { return false; };
+    const char *llrs_name = "llrs";                   // what the entry calls its input in the alignment's text
 };
 
 // Every batched min-sum entry is this function and what it passes to it.  The steps, in the order that is the ABI's:
 //   1 the error is cleared  2 opts are normalised  3 the code's range  4 early(): the entry's float pairs and quantiser, checked even
 //   for an empty batch  5 the empty batch is OK  6 "NULL buffer"  7 late(): the entry's integer triples  8 the caps are clamped
 //   9 support(variant, code): what the entry has no kernel for, EUNSUPPORTED with the arguments  10 the buffers, outputs in the order
-//   output, iters, success, [stage], [app]  11 a failed launch's status  12 the device checks: output % 8, app % 16, llrs % align.
+//   output, iters, success, [stage], [app]  11 a failed launch's status  12 the device checks: output % 8, app % 16, llrs % align,
+//   [mask % align].
 // launch(MsRun, the slice's MsBuffers, frames, stream) -> hipError_t enqueues the decode; it and `dev` are copied into the workers'
 // jobs of a sharded call, so they hold what they need by value.  Everything is a template parameter: nothing here allocates.
 template <class In, class A, class Early, class Late, class Support, class Launch>
@@ -158,11 +177,14 @@ int minsum_call(int code, MsBuffers<In, A> b, size_t batch, size_t max_iters, si
 
     const ldpc::CodeInfo &ci = ldpc::CODES[code];
     const int app_at = b.has_stage ? 4 : 3;
-    Buffers bufs{b.llrs, (size_t)ci.n * sizeof(In), {{b.output, (size_t)ci.output_len()}, {b.iters, sizeof(uint32_t)}, {b.success, 1}}};
+    const size_t row_bytes = (b.packed ? (size_t)ci.n / 8 : (size_t)ci.n) * sizeof(In);
+    Buffers bufs{b.llrs, row_bytes, {{b.output, (size_t)ci.output_len()}, {b.iters, sizeof(uint32_t)}, {b.success, 1}}};
+    if (b.mask) bufs.in2 = b.mask, bufs.in2_bytes = row_bytes;
     if (b.has_stage) bufs.out[3] = {b.stage, 1};
     bufs.out[app_at] = {b.app, ((size_t)ci.n + ci.p) * sizeof(A)};
-    auto slice_launch = [=](const void *in, void *const *out, size_t nb, hipStream_t st) {
+    auto slice_launch = [=](const void *in, const void *in2, void *const *out, size_t nb, hipStream_t st) {
         MsBuffers<In, A> s = b;
+        s.mask = (const In *)in2;
         s.llrs = (const In *)in, s.output = (uint8_t *)out[0], s.iters = (uint32_t *)out[1], s.success = (uint8_t *)out[2];
         if (b.has_stage) s.stage = (uint8_t *)out[3];
         if (b.app) s.app = (A *)out[app_at];
@@ -177,7 +199,9 @@ int minsum_call(int code, MsBuffers<In, A> b, size_t batch, size_t max_iters, si
         if ((uintptr_t)b.output % 8) return fail(LABRADOR_LDPC_HIP_EINVAL, "device output buffer must be 8-byte aligned");
         if (b.app && (uintptr_t)b.app % 16) return fail(LABRADOR_LDPC_HIP_EINVAL, "device app buffer must be 16-byte aligned");
         if (dev.llrs_align && (uintptr_t)b.llrs % dev.llrs_align)
-            return fail(LABRADOR_LDPC_HIP_EINVAL, "device llrs buffer must be %zu-byte aligned", dev.llrs_align);
+            return fail(LABRADOR_LDPC_HIP_EINVAL, "device %s buffer must be %zu-byte aligned", dev.llrs_name, dev.llrs_align);
+        if (b.mask && dev.llrs_align && (uintptr_t)b.mask % dev.llrs_align)
+            return fail(LABRADOR_LDPC_HIP_EINVAL, "device erasures buffer must be %zu-byte aligned", dev.llrs_align);
         return LABRADOR_LDPC_HIP_OK;
     };
     const bool direct_in = dev.reads_llrs_once(code, run.variant);

@@ -172,12 +172,15 @@ size_t chunk_items(size_t in_bytes_per_item)
     return c;
 }
 
-// launch(d_in, d_out[NOUT], first_item, n_items, stream) -> status code (0 = ok, error text set by the callee)
+// launch(d_in, d_in2, d_out[NOUT], first_item, n_items, stream) -> status code (0 = ok, error text set by the callee)
 // (direct_in: the kernel reads every input byte once, so the smallest calls may let it read the pinned buffer itself)
+// in2: a second input of in2_bytes_per_item per item, or NULL (then d_in2 is NULL): it is staged in the same device buffer as the
+// first, behind it at the next 16-byte boundary, by a copy of its own where the two are not adjacent on the host.
 template <int NOUT, class Launch>
 int host_pipeline(const void *in, size_t in_bytes_per_item, const HostOut *outs, size_t items,
-                  hipStream_t user_stream, Launch launch, bool direct_in = false)
+                  hipStream_t user_stream, Launch launch, bool direct_in = false, const void *in2 = nullptr, size_t in2_bytes_per_item = 0)
 {
+    if (!in2) in2_bytes_per_item = 0;
     static_assert(NOUT >= 1 && NOUT <= 5, "two staging sets of 1 + NOUT buffers share the 12 pool slots");
     constexpr int SET_SLOTS = NOUT <= 3 ? 4 : 1 + NOUT;        // pool slots per staging set
     // No stream given (the reference-shaped single-frame entries, every host-buffer call with opts == NULL): the calling THREAD's own
@@ -195,12 +198,14 @@ int host_pipeline(const void *in, size_t in_bytes_per_item, const HostOut *outs,
         size_t out_off[NOUT + 1];
         out_off[0] = 0;
         for (int o = 0; o < NOUT; ++o) out_off[o + 1] = (out_off[o] + items * outs[o].bytes_per_item + 15) / 16 * 16;
-        const size_t in_total = items * in_bytes_per_item, in_pad = (in_total + 15) / 16 * 16;
+        const size_t in1_total = items * in_bytes_per_item, in1_pad = (in1_total + 15) / 16 * 16, in2_total = items * in2_bytes_per_item;
+        const size_t in_total = in2 ? in1_pad + in2_total : in1_total, in_pad = (in_total + 15) / 16 * 16;
         if (in_pad + out_off[NOUT] <= SMALL_CALL_BYTES) {
             void *hbuf = nullptr, *dbuf_in = nullptr, *dbuf_out = nullptr;
             HIP_TRY(g_pinned.get(in_pad + out_off[NOUT], &hbuf));
             char *h_in = static_cast<char *>(hbuf), *h_out = h_in + in_pad;
-            std::memcpy(h_in, in, in_total);
+            std::memcpy(h_in, in, in1_total);
+            if (in2) std::memcpy(h_in + in1_pad, in2, in2_total);
             const bool direct = in_pad + out_off[NOUT] <= DIRECT_CALL_BYTES && g_pinned.dev != nullptr && direct_calls_enabled();
             char *const dev_in = static_cast<char *>(g_pinned.dev), *const dev_out = dev_in + in_pad;
             if (!(direct && direct_in)) {
@@ -216,7 +221,8 @@ int host_pipeline(const void *in, size_t in_bytes_per_item, const HostOut *outs,
             const bool ask = direct && direct_in && own_stream && notify_enabled();
             if (!ask || g_unsynced.on != user_stream) HIP_TRY(g_unsynced.retire());
             if (ask) ldpc::g_notify = ldpc::NotifyRequest{g_pinned.flag_dev(), g_pinned.ticket + 1, false};
-            const int st = launch(dbuf_in, d_outs, (size_t)0, items, user_stream);
+            void *const dbuf_in2 = in2 ? static_cast<char *>(dbuf_in) + in1_pad : nullptr;
+            const int st = launch(dbuf_in, dbuf_in2, d_outs, (size_t)0, items, user_stream);
             const bool notified = ldpc::g_notify.taken;
             ldpc::g_notify = ldpc::NotifyRequest{};
             if (notified) ++g_pinned.ticket;                  // (spent even if the launch then failed)
@@ -234,20 +240,23 @@ int host_pipeline(const void *in, size_t in_bytes_per_item, const HostOut *outs,
         }
     }
     HIP_TRY(g_unsynced.retire());
-    const size_t chunk_max = chunk_items(in_bytes_per_item);
+    const size_t chunk_max = chunk_items(in_bytes_per_item + in2_bytes_per_item);
     const size_t chunk = items < chunk_max ? items : chunk_max;
     const size_t nchunks = (items + chunk - 1) / chunk;
     const int nsets = nchunks > 1 ? 2 : 1;
-    void *d_in[2] = {}, *d_out[2][NOUT] = {};
+    void *d_in[2] = {}, *d_in2[2] = {}, *d_out[2][NOUT] = {};
+    const size_t in2_at = (chunk * in_bytes_per_item + 15) / 16 * 16;          // the second input's place in a staging set's input buffer
     for (int s = 0; s < nsets; ++s) {
-        HIP_TRY(g_pool.get(SET_SLOTS * s, chunk * in_bytes_per_item, &d_in[s]));
+        HIP_TRY(g_pool.get(SET_SLOTS * s, in2 ? in2_at + chunk * in2_bytes_per_item : chunk * in_bytes_per_item, &d_in[s]));
+        if (in2) d_in2[s] = static_cast<char *>(d_in[s]) + in2_at;
         for (int o = 0; o < NOUT; ++o) HIP_TRY(g_pool.get(SET_SLOTS * s + 1 + o, chunk * outs[o].bytes_per_item, &d_out[s][o]));
     }
-    const char *src = static_cast<const char *>(in);
+    const char *src = static_cast<const char *>(in), *src2 = static_cast<const char *>(in2);
 
     if (nchunks == 1) {
         HIP_TRY(hipMemcpyAsync(d_in[0], src, items * in_bytes_per_item, hipMemcpyHostToDevice, user_stream));
-        if (int st = launch(d_in[0], d_out[0], (size_t)0, items, user_stream)) return st;
+        if (in2) HIP_TRY(hipMemcpyAsync(d_in2[0], src2, items * in2_bytes_per_item, hipMemcpyHostToDevice, user_stream));
+        if (int st = launch(d_in[0], d_in2[0], d_out[0], (size_t)0, items, user_stream)) return st;
         for (int o = 0; o < NOUT; ++o)
             HIP_TRY(hipMemcpyAsync(outs[o].host, d_out[0][o], items * outs[o].bytes_per_item, hipMemcpyDeviceToHost, user_stream));
         HIP_TRY(hipStreamSynchronize(user_stream));
@@ -319,9 +328,10 @@ int host_pipeline(const void *in, size_t in_bytes_per_item, const HostOut *outs,
                 if (sh.abort) return LABRADOR_LDPC_HIP_OK;                     // the collector's status is reported below
             }
             HIP_TRY(hipMemcpyAsync(d_in[s], src + f0 * in_bytes_per_item, nb * in_bytes_per_item, hipMemcpyHostToDevice, ps.in));
+            if (in2) HIP_TRY(hipMemcpyAsync(d_in2[s], src2 + f0 * in2_bytes_per_item, nb * in2_bytes_per_item, hipMemcpyHostToDevice, ps.in));
             HIP_TRY(hipEventRecord(ps.ev_in[s], ps.in));
             HIP_TRY(hipStreamWaitEvent(s_run, ps.ev_in[s], 0));
-            if (int st = launch(d_in[s], d_out[s], f0, nb, s_run)) return st;
+            if (int st = launch(d_in[s], d_in2[s], d_out[s], f0, nb, s_run)) return st;
             HIP_TRY(hipEventRecord(ps.ev_run[s], s_run));
             {
                 std::lock_guard<std::mutex> lk(sh.m);

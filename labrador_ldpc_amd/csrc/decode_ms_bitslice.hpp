@@ -946,8 +946,14 @@ BS_FN void gather_planes(B &b, typename B::V p0, int stage, typename B::V (&X)[8
 // consecutive 16-byte pieces (a wave instruction reads 1 KB of whole lines: 256 LLRs of one codeword, M >= 256 in every code that is
 // built), non-temporal, the four loads of a half-column in flight before the first convert -- and every load's four bytes go to their
 // slab position with one dword store.  The slab then holds what the i8 source would have put there; nothing behind it knows.
-struct RawI8 { using T = int8_t; };
-struct QuantisedF32 { using T = float; float scale, lim; };
+//
+// PackedHard: the rows are HARD DECISIONS, [batch][N / 8] packed bits, MSB first, with an optional row of erasure bits
+// per frame in the same packing; the LLR of index j is 0 where its erasure bit is set, else -magnitude where its bit is set, else
+// +magnitude (1 .. 127).  A packed row already IS a sign plane, so this source has no byte slab, no byte gather and no transpose
+// (load_column_packed below): a block column of a group is 64 dwords, one per lane.
+struct RawI8 { using T = int8_t; static constexpr int row_len(int n) { return n; } };
+struct QuantisedF32 { using T = float; float scale, lim; static constexpr int row_len(int n) { return n; } };
+struct PackedHard { using T = uint8_t; uint32_t magnitude; const uint8_t *erasures; static constexpr int row_len(int n) { return n / 8; } };
 
 // the f32 source's half of load_column_planes: block column c of the group's f32 rows, quantised, into the skewed slab
 template <int CODE, class B, class D>
@@ -984,6 +990,70 @@ BS_FN void stage_column_quantised(B &b, const D &d, const float *llrs, int c, ui
     });
 }
 
+// The packed source's whole load_column_planes: block column c of the group's packed rows -> the lane's 8 bit planes.
+//  * A block column of a group is G * M = 2048 bits = 64 dwords in every code that is built: lane i loads dword i, which holds slab
+//    positions 32 i .. 32 i + 31 (p = codeword * M + index), whole 128-byte lines per wave instruction, and puts it at word i of the
+//    staging slab; the erasure row's dword goes to word 64 + i.  The loads are unconditional, as the i8 source's: lanes of codewords
+//    beyond the batch read the group's first frame and the value is masked.
+//  * Lane (cw, q, ll) wants, for bit b, position cw * M + q * Q + ll + L * b: dword cw * W + q * L + b / K of the slab (K = 32 / L bits
+//    from each of L dwords; the lanes of a quarter read the same L words, a broadcast), index ll + L * (b mod K) inside it -- which is
+//    bit index ^ 7 of the little-endian dword, the bytes being MSB first.  index ^ 7 = (ll ^ (7 & (L - 1))) + ((L k) ^ (7 & ~(L - 1))):
+//    one shift by the lane's part per dword, then constant bit picks.
+//  * From the sign word S and the erasure word E: plane k of the i8 value is S where bit k of 256 - magnitude is set, ~S where bit k of
+//    magnitude is set (both: all ones, neither: zero), the sign plane is S, and all eight are cleared where E is set and for codewords
+//    beyond the batch.  The bits of the magnitude are wave-uniform constant planes, as the corrected form's multiplier bits are.
+// No mask (erasures == nullptr) is a wave-uniform branch around the second load and its picks.
+template <int CODE, class B, class D>
+BS_FN void load_column_packed(B &b, const D &d, const uint8_t *rows, int c, uint32_t group, uint32_t batch, int stage, typename B::V (&X)[8],
+                              PackedHard source)
+{
+    using GEO = Geo<CODE>;
+    using V = typename B::V;
+    constexpr int M = GEO::M, N = GEO::N, L = GEO::L, W = GEO::W, G = GEO::G, K = 32 / L;
+    constexpr int ROW = N / 8, LANE_X = 7 & (L - 1), PICK_X = 7 & ~(L - 1);
+    static_assert(G * M == 2048 && L >= 2 && L <= 16 && ROW % 4 == 0 && (M / 8) % 4 == 0, "64 aligned dwords per block column of a group");
+    static_assert(2 * 256 <= STAGE_BYTES, "the sign and erasure words fit the staging slab");
+    // (an opaque copy of the lane index, as in stage_column_quantised: what is formed from it stays inside this use)
+    V lane = d.lane;
+    B::pin(lane);
+    const V pcw = B::shr(lane, ilog2c(M / 32));                                              // the codeword of the lane's dword inside the group
+    const V ok = B::less_u(B::add(B::c(group * (uint32_t)G), pcw), B::c(batch));
+    const V src = B::add(B::mul_u(B::and_(pcw, ok), (uint32_t)ROW), B::add(B::c((uint32_t)c * (M / 8)), B::and_(B::shl(lane, 2), B::c(M / 8 - 1))));
+    const V at = B::add(B::shl(lane, 2), B::c(stage));
+    const bool masked = source.erasures != nullptr;
+    b.lds_write32(at, B::and_(B::gload32(rows, src), ok));
+    if (masked) b.lds_write32(B::add(at, B::c(256)), B::and_(B::gload32(source.erasures + (size_t)group * G * ROW, src), ok));
+    // (compiler fences around the slab's use, as in load_column_planes)
+    B::mem_fence();
+    const V sh = B::xor_(B::and_(lane, B::c(L - 1)), B::c(LANE_X));
+    const V qbase = B::add(B::shl(B::and_(lane, B::c(~(L - 1) & 63)), 2), B::c(stage));      // the quarter's first word: (cw * W + q * L) * 4
+    auto pick = [&](int words) {
+        V r = B::c(0);
+        sfor<0, L>([&](auto J_) {
+            constexpr int j = decltype(J_)::value;
+            const V w = B::shr_v(b.lds_read32(B::add(qbase, B::c(words + 4 * j))), sh);
+            sfor<0, K>([&](auto K_) {
+                constexpr int k = decltype(K_)::value;
+                r = B::or_(r, B::shl(B::and_(B::shr(w, (L * k) ^ PICK_X), B::c(1)), j * K + k));
+            });
+        });
+        return r;
+    };
+    const V S = pick(0);
+    V E = B::c(0);
+    if (masked) E = pick(256);
+    B::mem_fence();
+    const V valid = B::less_u(B::add(B::c(group * (uint32_t)G), B::shr(lane, ilog2c(W))), B::c(batch));
+    const V keep = B::andn(valid, E);
+    const uint32_t pos = source.magnitude, neg = 256u - source.magnitude;
+    sfor<0, 7>([&](auto K_) {
+        constexpr int k = decltype(K_)::value;
+        const V a = B::c(0u - ((neg >> k) & 1u)), p = B::c(0u - ((pos >> k) & 1u));         // the two values' bit k as constant planes
+        X[k] = B::and_(B::or_(B::and_(S, a), B::andn(p, S)), keep);
+    });
+    X[7] = B::and_(S, keep);
+}
+
 template <int CODE, class B, class D, class SRC = RawI8>
 BS_FN void load_column_planes(B &b, const D &d, const typename SRC::T *llrs, int c, uint32_t group, uint32_t batch, int stage, typename B::V (&X)[8],
                               SRC source = {})
@@ -991,6 +1061,10 @@ BS_FN void load_column_planes(B &b, const D &d, const typename SRC::T *llrs, int
     using GEO = Geo<CODE>;
     using V = typename B::V;
     constexpr int M = GEO::M, N = GEO::N, Q = GEO::Q, W = GEO::W, G = GEO::G;
+    if constexpr (std::is_same_v<SRC, PackedHard>) {
+        load_column_packed<CODE>(b, d, llrs, c, group, batch, stage, X, source);      // (no byte slab: nothing below is reached)
+        return;
+    }
     if constexpr (std::is_same_v<SRC, QuantisedF32>) stage_column_quantised<CODE>(b, d, llrs, c, group, batch, stage, source);
     else
         sfor<0, 2>([&](auto H_) {
@@ -1163,7 +1237,8 @@ BS_FN void init_kernel(B &b)
 // llrs [batch][N] i8, output [batch][NP/8] MSB first, iters [batch], success [batch]; `group` = index of the group of G frames.
 // (Lane offsets are relative to the group's first frame, so they fit 32 bits whatever the batch.)
 // SOFT: app [batch][NP] i8 receives every frame's marginals as well (store_marginals).
-// SRC: what the rows of llrs are (load_column_planes): i8, or f32 [batch][N] that the loader quantises at `source`.
+// SRC: what the rows of llrs are (load_column_planes): i8, f32 [batch][N] that the loader quantises at `source`, or packed hard
+// decisions [batch][N / 8] at `source`'s magnitude and erasure rows (rows of SRC::row_len(N) elements).
 template <int CODE, class B, bool CORRECTED = false, int MULBITS = 8, bool SOFT = false, class SRC = RawI8>
 BS_FN void decode_group(B &b, const typename SRC::T *llrs_all, uint8_t *output_all, uint32_t *iters_all, uint8_t *success_all, uint32_t batch,
                         uint32_t maxiters, uint32_t group, uint32_t scale_num = 1, uint32_t scale_shift = 0, uint32_t offset = 0,
@@ -1177,7 +1252,7 @@ BS_FN void decode_group(B &b, const typename SRC::T *llrs_all, uint8_t *output_a
     d.init_lane(b);
     const V lane = d.lane;
     const V cw = B::shr(lane, ilog2c(W));                                    // codeword of the lane inside the group (0 for W = 64)
-    const typename SRC::T *llrs = llrs_all + (size_t)group * G * GEO::N;
+    const typename SRC::T *llrs = llrs_all + (size_t)group * G * SRC::row_len(GEO::N);
     uint8_t *output = output_all + (size_t)group * G * GEO::OUT_LEN;
     uint32_t *iters = iters_all + (size_t)group * G;
     uint8_t *success = success_all + (size_t)group * G;

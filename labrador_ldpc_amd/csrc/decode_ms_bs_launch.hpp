@@ -1,5 +1,5 @@
-// decode_ms_bs_launch.hpp -- the one lockstep launch path of the bit-sliced i8 min-sum kernels: what the six decode_ms_bs*.hip files
-// (plain, corrected, soft, corrected soft, f32-reading, f32-reading soft) share around their kernels.  Host text.
+// decode_ms_bs_launch.hpp -- the one lockstep launch path of the bit-sliced i8 min-sum kernels: what the seven decode_ms_bs*.hip files
+// (plain, corrected, soft, corrected soft, f32-reading, f32-reading soft, packed-hard-reading) share around their kernels.  Host text.
 //
 // A file describes its FORM and this header does the rest:
 //     struct Form {

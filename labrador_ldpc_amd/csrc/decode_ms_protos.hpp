@@ -58,6 +58,18 @@ hipError_t launch_decode_ms_bitsliced_quantised_corrected(int code, const float 
                                                           size_t batch, uint32_t maxiters, float scale, int lim, uint32_t scale_num,
                                                           uint32_t scale_shift, uint32_t offset, hipStream_t stream);
 
+// The bit-sliced i8 flooding kernels of the one-wave TM codes reading PACKED HARD DECISIONS (decode_ms_bs_hard.hip):
+// input [batch][n / 8] packed bits MSB first, erasures nullptr or the same shape; the loader builds the planes of the i8 frame that is 0
+// where erased, else -magnitude where the bit is set, else +magnitude (1 .. 127, already range-checked); per frame the three results are
+// those of the i8 kernel -- plain, or corrected at the caller's triple -- on that frame.  Lockstep kernels at every batch size; input,
+// erasures and output 4-byte aligned (the caller checks input and erasures at 4, output at 8).  hipErrorInvalidConfiguration for any other code (bs::bitsliced_soft_code)
+// and in a 16-plane experiment build.
+hipError_t launch_decode_ms_bitsliced_hard(int code, const uint8_t *input, const uint8_t *erasures, uint8_t *output, uint32_t *iters,
+                                           uint8_t *success, size_t batch, uint32_t maxiters, uint32_t magnitude, hipStream_t stream);
+hipError_t launch_decode_ms_bitsliced_hard_corrected(int code, const uint8_t *input, const uint8_t *erasures, uint8_t *output, uint32_t *iters,
+                                                     uint8_t *success, size_t batch, uint32_t maxiters, uint32_t magnitude, uint32_t scale_num,
+                                                     uint32_t scale_shift, uint32_t offset, hipStream_t stream);
+
 // ... with soft output as well (decode_ms_bs_quantised_soft.hip): the four results are those of
 // launch_decode_ms_bitsliced_soft / launch_decode_ms_bitsliced_corrected_soft on the frame quantised that way, app [batch][n + p] i8
 // 16-byte aligned.

@@ -35,6 +35,10 @@ the TM codes); NUM/DEN and the offset as `--fixed-scale` / `--fixed-offset`; any
 kernels' own loader (labrador_ldpc_decode_ms_bitsliced_quantised_batch_i8 / _corrected_batch_i8 /
 labrador_ldpc_decode_ms_cascade_bitsliced_quantised_batch_i8, DESIGN.md 4.19: TM1536, TM2048, TM6144, TM8192); on the flooding schedule
 it is the only `--from-f32` decode, with or without `--fixed-flooding-scale` / `--fixed-flooding-offset`.
+`--llr hard` (`--schedule flooding` only) reduces the f32 frames of the f32 branch to their signs on the device
+(labrador_ldpc_llrs_to_hard_batch_f32) and decodes the packed bits at `--hard-magnitude M` (1 .. 127, default 1) through the bit-sliced
+kernels' packed loader (labrador_ldpc_decode_ms_bitsliced_hard_batch_i8 / _corrected_batch_i8, DESIGN.md 4.21: TM1536, TM2048, TM6144,
+TM8192), with or without `--fixed-flooding-scale` / `--fixed-flooding-offset`: what a hard-decision receiver gets from min-sum.
 
 Noise conventions:
   --noise perftest  sigma = 10^(-snr_db/10), what the reference calls "snr" (perftest/src/main.rs:15)
@@ -64,7 +68,7 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
               scale: float = 1.0, offset: float = 0.0, llr: str = "f32", llr_scale: float = 8.0, llr_lim: int = 31,
               scale_num=None, scale_shift=None, fixed_offset=None, max_sweeps=None, from_f32: bool = False,
               flooding_scale: float = 1.0, flooding_offset: float = 0.0, flooding_scale_num=None, flooding_scale_shift=None,
-              flooding_fixed_offset=None, bitsliced_loader: bool = False):
+              flooding_fixed_offset=None, bitsliced_loader: bool = False, hard_magnitude: int = 1):
     """One SNR point.  Returns (trials, bits, errors, ber, frame_errors).  `schedule`: "flooding" (decode_ms_batch, the
     reference's decoder) or "layered" (decode_ms_layered_batch).  `scale`, `offset`: the layered schedule's normalized / offset
     min-sum correction (the defaults are plain min-sum); the flooding decoder has none.  `llr`: "f32", or "i8" / "i16" for the
@@ -82,11 +86,19 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
     triple; `llr` "i8" on the flooding schedule -- the only i8 flooding decode here -- and as the cascade's first stage, `from_f32`
     included there; None, the default, is none).  `bitsliced_loader` (`from_f32`, `llr` "i8", flooding or cascade): the f32 frames go
     through decode_ms_quantised_batch / decode_ms_cascade_quantised_batch with bitsliced=True -- on the flooding schedule with the
-    flooding triple, if one is given."""
+    flooding triple, if one is given.  `llr` "hard" (flooding schedule only): the f32 frames reduced to their signs by
+    llrs_to_hard_batch and decoded by decode_ms_hard_batch at `hard_magnitude`, with the flooding triple, if one is given; nothing else
+    goes with it."""
+    if llr == "hard" and (schedule != "flooding" or from_f32 or bitsliced_loader or max_sweeps is not None or scale != 1.0 or offset != 0.0
+                          or flooding_scale != 1.0 or flooding_offset != 0.0
+                          or not (scale_num is None and scale_shift is None and fixed_offset is None)):
+        raise ValueError("hard LLRs belong to the flooding schedule, with hard_magnitude and the i8 flooding triple alone")
+    if llr != "hard" and hard_magnitude != 1:
+        raise ValueError("hard_magnitude belongs to hard LLRs")
     if bitsliced_loader and not (from_f32 and llr == "i8" and schedule in ("flooding", "cascade")):
         raise ValueError("bitsliced_loader belongs to from_f32 with i8 LLRs on the flooding schedule and the cascade")
     fixed_flooding = not (flooding_scale_num is None and flooding_scale_shift is None and flooding_fixed_offset is None)
-    if fixed_flooding and (llr != "i8" or schedule == "layered" or (from_f32 and schedule != "cascade" and not bitsliced_loader)):
+    if fixed_flooding and llr != "hard" and (llr != "i8" or schedule == "layered" or (from_f32 and schedule != "cascade" and not bitsliced_loader)):
         raise ValueError("flooding_scale_num, flooding_scale_shift and flooding_fixed_offset belong to i8 LLRs on the flooding schedule "
                          "and the cascade")
     if fixed_flooding and schedule == "flooding" and not (scale_num is None and scale_shift is None and fixed_offset is None):
@@ -97,9 +109,10 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
         raise ValueError("scale and offset belong to the layered schedule")
     if schedule != "cascade" and max_sweeps is not None:
         raise ValueError("max_sweeps belongs to the cascade")
-    if llr not in FLOAT_LLRS + ("i8", "i16"):
+    if llr not in FLOAT_LLRS + ("i8", "i16", "hard"):
         raise ValueError(f"unknown LLR type {llr!r}")
-    if llr not in FLOAT_LLRS and ((schedule == "flooding" and not fixed_flooding and not bitsliced_loader) or scale != 1.0 or offset != 0.0):
+    if llr not in FLOAT_LLRS + ("hard",) and ((schedule == "flooding" and not fixed_flooding and not bitsliced_loader) or scale != 1.0
+                                               or offset != 0.0):
         raise ValueError("quantised LLRs belong to the layered schedule without scale and offset")
     if llr in FLOAT_LLRS and not (scale_num is None and scale_shift is None and fixed_offset is None):
         raise ValueError("scale_num, scale_shift and fixed_offset belong to the quantised LLRs of the layered schedule")
@@ -134,6 +147,10 @@ def ms_trials(code, snr_db: float, noise: str = "perftest", maxiters: int = 100,
                 out = decode(llrs, llr, llr_scale, llr_lim, maxiters, scale_num=scale_num, scale_shift=scale_shift, offset=fixed_offset,
                              **({"max_sweeps": max_sweeps, **flooding_kw, **({"bitsliced": True} if bitsliced_loader else {})}
                                 if schedule == "cascade" else {}))[0]
+        elif llr == "hard":                                                  # the f32 branch's frames, reduced to their signs
+            hard = code.llrs_to_hard_batch(code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds))
+            triple = dict(zip(("scale_num", "scale_shift", "offset"), flooding_kw.values()))
+            out = code.decode_ms_hard_batch(hard, maxiters, hard_magnitude, **triple)[0]
         elif llr not in FLOAT_LLRS:                                          # the same noise, quantised by the i8 channel kernel
             llrs = code.awgn_frames(cw, batch, sigma, seed=(seed << 20) + rounds, dtype="i8", scale=llr_scale, lim=llr_lim)
             if schedule == "flooding":                                       # (i8 with a flooding triple: checked above)
@@ -193,9 +210,11 @@ def main(argv=None):
                     help="normalized min-sum factor of the flooding decoder, 0 < scale <= 1 (--schedule flooding / cascade, --llr f32)")
     ap.add_argument("--flooding-offset", type=float, default=0.0,
                     help="offset min-sum term of the flooding decoder in LLR units, >= 0 (--schedule flooding / cascade, --llr f32)")
-    ap.add_argument("--llr", choices=["f32", "f16", "bf16", "i8", "i16"], default="f32",
+    ap.add_argument("--llr", choices=["f32", "f16", "bf16", "i8", "i16", "hard"], default="f32",
                     help="LLR type; i8 / i16: the fixed-point layered decoder on quantised frames (--schedule layered); "
-                         "f16 / bf16: the f32 frames rounded to the format, through the half-precision entries")
+                         "f16 / bf16: the f32 frames rounded to the format, through the half-precision entries; "
+                         "hard: the f32 frames' signs as packed bits, through the bit-sliced kernels' packed loader (--schedule flooding)")
+    ap.add_argument("--hard-magnitude", type=int, default=1, metavar="M", help="the LLR magnitude of a hard decision, 1 .. 127 (--llr hard)")
     ap.add_argument("--llr-scale", type=float, default=8.0, help="quantiser: clamp(rint(scale * y), +-lim) (--llr i8 / i16)")
     ap.add_argument("--llr-lim", type=int, default=31, help="quantiser limit, at most 127 (--llr i8 / i16)")
     ap.add_argument("--fixed-scale", type=fixed_scale, default=None, metavar="NUM/DEN",
@@ -211,6 +230,11 @@ def main(argv=None):
     ap.add_argument("--bitsliced-loader", action="store_true",
                     help="decode the f32 frames through the bit-sliced kernels' own loader (--from-f32 --llr i8, --schedule flooding / cascade)")
     args = ap.parse_args(argv)
+    if args.llr == "hard" and (args.schedule != "flooding" or args.from_f32 or args.bitsliced_loader or args.flooding_scale != 1.0
+                               or args.flooding_offset != 0.0 or args.fixed_scale is not None or args.fixed_offset is not None):
+        ap.error("--llr hard needs --schedule flooding and takes --hard-magnitude, --fixed-flooding-scale and --fixed-flooding-offset alone")
+    if args.llr != "hard" and args.hard_magnitude != 1:
+        ap.error("--hard-magnitude needs --llr hard")
     if args.bitsliced_loader and not (args.from_f32 and args.llr == "i8" and args.schedule in ("flooding", "cascade")):
         ap.error("--bitsliced-loader needs --from-f32 --llr i8 and --schedule flooding or cascade")
     if args.from_f32 and (args.llr in FLOAT_LLRS or (args.schedule == "flooding" and not args.bitsliced_loader)):
@@ -220,7 +244,7 @@ def main(argv=None):
     if args.schedule != "cascade" and args.max_sweeps is not None:
         ap.error("--max-sweeps needs --schedule cascade")
     fixed_flooding = args.fixed_flooding_scale is not None or args.fixed_flooding_offset is not None
-    if args.llr not in FLOAT_LLRS and ((args.schedule == "flooding" and not fixed_flooding and not args.bitsliced_loader) or args.scale != 1.0 or args.offset != 0.0):
+    if args.llr not in FLOAT_LLRS + ("hard",) and ((args.schedule == "flooding" and not fixed_flooding and not args.bitsliced_loader) or args.scale != 1.0 or args.offset != 0.0):
         ap.error("--llr i8 / i16 needs --schedule layered without --scale and --offset")
     if args.llr in FLOAT_LLRS and (args.fixed_scale is not None or args.fixed_offset is not None):
         ap.error("--fixed-scale and --fixed-offset need --schedule layered --llr i8 / i16")
@@ -238,7 +262,7 @@ def main(argv=None):
                                                   from_f32=args.from_f32, flooding_scale=args.flooding_scale,
                                                   flooding_offset=args.flooding_offset, flooding_scale_num=fl_num,
                                                   flooding_scale_shift=fl_shift, flooding_fixed_offset=args.fixed_flooding_offset,
-                                                  bitsliced_loader=args.bitsliced_loader)
+                                                  bitsliced_loader=args.bitsliced_loader, hard_magnitude=args.hard_magnitude)
         print(f"{code.name},{snr:.2f},{trials},{bits},{max(1, errors)},{ber:.5e}", flush=True)
     return 0
 
