@@ -18,7 +18,6 @@ the last replay once more with nothing touched.  Every result is compared bit fo
 
 The cascades, decode_ms_quantised_batch without bitsliced=True and the half-precision flooding entries are never called under capture
 here: the header forbids it."""
-import functools
 import os
 import subprocess
 import sys
@@ -34,36 +33,16 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):               # (the child proces
 
 import captured  # noqa: E402
 import edge_frames  # noqa: E402
-import flooding_corrected_restatement as flc  # noqa: E402
-import flooding_fixed_corrected_soft_restatement as ffs  # noqa: E402
+from entry_table import (BS_GROUP, C, CAPS, QUANT, TRIPLE, decode_reference, decoder_results, entries, ffs, flooding_structure,  # noqa: E402
+                         host_rows, pool_of, small_pool, small_reference, streaming_cases, torch_dtype, triple_kw, windows)
 import hard_frames  # noqa: E402
 import labrador_ldpc_amd as la  # noqa: E402
-from labrador_ldpc_amd import LDPCCode  # noqa: E402
-import layered_corrected_restatement as lcr  # noqa: E402
-import layered_fixed_corrected_restatement as fcr  # noqa: E402
-import layered_fixed_restatement as fr  # noqa: E402
-import layered_helpers  # noqa: E402
-import layered_restatement as lr  # noqa: E402
 import oracle  # noqa: E402
 import quantise_restatement as qr  # noqa: E402
-import quantised_layered_restatement as qlr  # noqa: E402
-from test_gpu_half_llrs import round_to, widen  # noqa: E402
-from test_gpu_layered_fixed import codewords_per_workgroup  # noqa: E402
-from test_gpu_quantised_layered import PARAMS as QUANT, edge_rows  # noqa: E402
-from test_gpu_soft_edges import flooding_grid_bound  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-C = LDPCCode
-CAPS = (0, 1, 25)
 MANY_CAP = 20
-NP = {"f32": np.float32, "f64": np.float64, "i8": np.int8, "i16": np.int16, "i32": np.int32}
-PAIR = (0.8125, 0.125)                                      # (scale, offset) of the f32 corrections on G + 1 frames
-TRIPLE = (13, 4, 0)
-BS_GROUP = {C.TM1280: 16, C.TM1536: 8, C.TM2048: 4, C.TM5120: 4, C.TM6144: 2, C.TM8192: 1}     # BsPlan<CODE>::G
-ONE_WAVE = (C.TM1536, C.TM2048, C.TM6144, C.TM8192)
-TWO_WAVES = (C.TM1280, C.TM5120)
-BS = 64                                                      # LABRADOR_LDPC_HIP_VARIANT_BITSLICE
 HIP_STREAM_PER_THREAD = 2                                    # the handle's value in HIP
 
 
@@ -75,218 +54,8 @@ def gpu():
     torch.cuda.set_device(0)
 
 
-# ---- input pools --------------------------------------------------------------------------------------------------------------------------
-def awgn(code, rng, frames, ebn0, kind):
-    if kind == "i32":
-        return oracle.awgn_llrs(code, rng, frames, ebn0, np.int32, scale=3e8, lim=2 ** 31 - 1)[0]
-    return oracle.awgn_llrs(code, rng, frames, ebn0, NP.get(kind, np.float32))[0]
-
-
-def float_extras(code, rng, dt):
-    """one frame with NaN LLRs and one with +inf and -inf ones"""
-    x = oracle.awgn_llrs(code, rng, 2, 3.0, dt)[0]
-    x[0, rng.choice(code.n(), 5, replace=False)] = np.nan
-    x[1, ::7] = np.inf
-    x[1, 3::11] = -np.inf
-    return x
-
-
-def pool_of(code, kind, each, seed):
-    """(frames, kind of each): `each` converging frames at 4 dB (kind 0), `each` at 0 dB that never converge (1), `each` edge-valued
-    (2: edge_frames' rows of the type; "q-i8" / "q-i16", f32 for the quantiser at that type's scale: edge_rows of
-    tests/test_gpu_quantised_layered.py), and for f32 / f64 a NaN and a +-inf frame (3); interleaved by kind."""
-    rng = np.random.default_rng(seed)
-    conv, fail = awgn(code, rng, each, 4.0, kind), awgn(code, rng, each, 0.0, kind)
-    if kind.startswith("q-"):
-        parts = [conv, fail, edge_rows(code, kind[2:], rng, each), float_extras(code, rng, np.float32)]
-    elif kind in ("f32", "f64"):
-        rows = edge_frames.whole_frame_rows(code, NP[kind], rng)
-        parts = [conv, fail, rows[[5, 3, 2, 8, 4, 0, 1, 6, 7][:each]], float_extras(code, rng, NP[kind])]
-    else:
-        rows = edge_frames.integer_range_rows(code, NP[kind], rng, 3)
-        parts = [conv, fail, rows[np.arange(each) * (len(rows) // each) % len(rows)]]
-    kinds = np.concatenate([np.full(len(x), k) for k, x in enumerate(parts)])
-    order = np.argsort(np.concatenate([np.arange(len(x)) for x in parts]), kind="stable")
-    x = np.ascontiguousarray(np.concatenate(parts)[order])
-    x.setflags(write=False)
-    return x, kinds[order]
-
-
-@functools.lru_cache(maxsize=None)
-def small_pool(code, kind):
-    """8 frames (f32, f64, q-*) or 6 (integers) for the G + 1 cases.  "f16" / "bf16": the f32 pool rounded to the format, as
-    (bits uint16, kinds); small_values() widens them."""
-    if kind in ("f16", "bf16"):
-        x, kinds = small_pool(code, "f32")
-        with np.errstate(over="ignore"):
-            return round_to(x, kind), kinds
-    return pool_of(code, kind, 2, 0xCA90 + 64 * int(code) + sorted(list(NP) + ["q-i8", "q-i16"]).index(kind))
-
-
-def small_values(code, kind):
-    """what the reference decodes: the pool, widened where it is halves"""
-    x = small_pool(code, kind)[0]
-    return widen(x, kind) if kind in ("f16", "bf16") else x
-
-
-_ST = {}
-
-
-def flooding_structure(code, module):
-    if (module, code) not in _ST:
-        _ST[module, code] = module.Structure(int(code)) if module is flc else module.structure(int(code))
-    return _ST[module, code]
-
-
-def decode_reference(family, code, y, cap, params):
-    """(output, iters, success, marginals) of `family`'s CPU statement on the frames y"""
-    if family == "flooding":
-        return oracle.decode_ms_soft_batch(code, y, cap)
-    if family == "flooding-corrected":
-        return flc.decode_flooding_corrected(flooding_structure(code, flc), y, cap, *params)
-    if family == "layered":
-        st = layered_helpers.structure(code, lr.Structure)
-        return lr.decode_layered(st, y, cap) if params is None else lcr.decode_layered_corrected(st, y, cap, *params)
-    if family == "fixed":
-        st = layered_helpers.structure(code, fr.Structure)
-        return (fr.decode_fixed(st, y, cap) if qlr.identity(params) else fcr.decode_fixed_corrected(st, y, cap, *params))[:4]
-    if family == "quantised-layered":
-        suf, triple = params
-        return qlr.layered_quantised(code, y, NP[suf], *QUANT[suf], cap, triple)[:4]
-    if family == "bitsliced":                                # i8 flooding; f32 frames go through the quantiser's statement first
-        lim, triple = params
-        q = y if y.dtype == np.int8 else qr.quantise(y, np.int8, 8.0, lim)
-        if triple is None:
-            return oracle.decode_ms_soft_batch(code, q, cap)
-        return ffs.decode(flooding_structure(code, ffs), q, cap, *triple)
-    raise KeyError(family)
-
-
-@functools.lru_cache(maxsize=None)
-def small_reference(family, code, kind, cap, params):
-    ref = decode_reference(family, code, small_values(code, kind), cap, params)
-    kinds = small_pool(code, kind)[1]
-    if cap == max(CAPS):                                     # the pool still exercises early exit and full-length decodes
-        assert ref[2][kinds == 0].all(), (family, code.name, kind, params, "a 4 dB frame fails", ref[2].tolist())
-        assert not ref[2][kinds == 1].any(), (family, code.name, kind, params, "a 0 dB frame converges", ref[2].tolist())
-        assert (ref[1][kinds == 1] == cap).all()
-    return ref
-
-
-def windows(pool_len, frames):
-    """index sets of `frames` consecutive pool entries (wrapping), enough of them to pass through the whole pool, two at the least"""
-    count = max(2, -(-pool_len // frames))
-    return [np.arange(k * frames, (k + 1) * frames) % pool_len for k in range(count)]
-
-
 # ---- the entries on G + 1 frames ----------------------------------------------------------------------------------------------------------
-class Entry:
-    def __init__(self, name, code, kind, g, call, family, params, soft, app="same", note=""):
-        self.id = "-".join(x for x in (name, kind, note, code.name) if x)
-        self.code, self.kind, self.g, self.call, self.family, self.params, self.soft, self.app = code, kind, g, call, family, params, soft, app
-
-
-def triple_kw(t):
-    return {} if t is None else dict(scale_num=t[0], scale_shift=t[1], offset=t[2])
-
-
-def entries():
-    out = []
-    layered_g = lambda c: layered_helpers.layered_grid_bound(c, 1)[1]                                              # noqa: E731
-    # flooding soft output, the f32-pipe kernels
-    for kind, codes in (("f32", (C.TC256, C.TM8192)), ("i8", (C.TC256, C.TM8192)), ("i16", (C.TC256, C.TM8192)),
-                        ("i32", (C.TC256, C.TM8192)), ("f64", (C.TC256,))):
-        for code in codes:
-            out.append(Entry("decode_ms_soft_batch", code, kind, flooding_grid_bound(code, NP[kind], 0, 1)[1],
-                             lambda c, x, cap, b: c.decode_ms_soft_batch(x, cap, **b), "flooding", None, True))
-    # layered f32, plain and corrected; f16 / bf16 through the same methods (the loader widens)
-    for kind, codes in (("f32", (C.TC128, C.TM2048, C.TM8192)), ("f16", (C.TC128, C.TM2048)), ("bf16", (C.TC128, C.TM2048))):
-        for code in codes:
-            for pair in (None, PAIR):
-                kw = {} if pair is None else dict(scale=pair[0], offset=pair[1])
-                note = "plain" if pair is None else "scale-offset"
-                out.append(Entry("decode_ms_layered_batch", code, kind, layered_g(code),
-                                 lambda c, x, cap, b, kw=kw: c.decode_ms_layered_batch(x, cap, **b, **kw), "layered", pair, False, note=note))
-                out.append(Entry("decode_ms_layered_soft_batch", code, kind, layered_g(code),
-                                 lambda c, x, cap, b, kw=kw: c.decode_ms_layered_soft_batch(x, cap, **b, **kw), "layered", pair, True,
-                                 app="f32", note=note))
-    # fixed-point layered: the plain entry, an identity triple and (13, 4, 0); then the same behind the quantising loader
-    for code in (C.TC128, C.TM8192):
-        for kind in ("i8", "i16"):
-            for triple, note in ((None, "plain"), ((16, 4, 0), "identity"), (TRIPLE, "13-4-0")):
-                kw = triple_kw(triple)
-                out.append(Entry("decode_ms_layered_fixed_batch", code, kind, codewords_per_workgroup(code),
-                                 lambda c, x, cap, b, kw=kw: c.decode_ms_layered_fixed_batch(x, cap, **b, **kw), "fixed", triple, False, note=note))
-                out.append(Entry("decode_ms_layered_fixed_soft_batch", code, kind, codewords_per_workgroup(code),
-                                 lambda c, x, cap, b, kw=kw: c.decode_ms_layered_fixed_soft_batch(x, cap, **b, **kw), "fixed", triple, True,
-                                 app="i32", note=note))
-            for triple, note in ((None, "plain"), (TRIPLE, "13-4-0")):
-                kw, suf = triple_kw(triple), kind
-                out.append(Entry("decode_ms_layered_quantised_batch", code, "q-" + suf, codewords_per_workgroup(code),
-                                 lambda c, x, cap, b, kw=kw, suf=suf: c.decode_ms_layered_quantised_batch(x, suf, *QUANT[suf], cap, **b, **kw),
-                                 "quantised-layered", (suf, triple), False, note=note))
-                out.append(Entry("decode_ms_layered_quantised_soft_batch", code, "q-" + suf, codewords_per_workgroup(code),
-                                 lambda c, x, cap, b, kw=kw, suf=suf: c.decode_ms_layered_quantised_soft_batch(x, suf, *QUANT[suf], cap, **b, **kw),
-                                 "quantised-layered", (suf, triple), True, app="i32", note=note))
-    # corrected f32 flooding
-    for code in (C.TC256, C.TM2048, C.TM8192):
-        kw = dict(scale=PAIR[0], offset=PAIR[1])
-        g = flooding_grid_bound(code, np.float32, 0, 1)[1]
-        out.append(Entry("decode_ms_batch", code, "f32", g, lambda c, x, cap, b, kw=kw: c.decode_ms_batch(x, cap, **b, **kw),
-                         "flooding-corrected", PAIR, False, note="scale-offset"))
-        out.append(Entry("decode_ms_soft_batch", code, "f32", g, lambda c, x, cap, b, kw=kw: c.decode_ms_soft_batch(x, cap, **b, **kw),
-                         "flooding-corrected", PAIR, True, note="scale-offset"))
-    # bit-sliced i8, the one-wave codes
-    for code in ONE_WAVE:
-        g = BS_GROUP[code]
-        out.append(Entry("decode_ms_corrected_fixed_batch", code, "i8", g,
-                         lambda c, x, cap, b: c.decode_ms_corrected_fixed_batch(x, *TRIPLE, cap, **b), "bitsliced", (127, TRIPLE), False))
-        for triple, note in ((None, "plain"), (TRIPLE, "corrected")):
-            kw = triple_kw(triple)
-            out.append(Entry("decode_ms_bitsliced_soft_batch", code, "i8", g,
-                             lambda c, x, cap, b, kw=kw: c.decode_ms_bitsliced_soft_batch(x, cap, **b, **kw), "bitsliced", (127, triple), True,
-                             note=note))
-            out.append(Entry("decode_ms_quantised_batch", code, "q-i8", g,
-                             lambda c, x, cap, b, kw=kw: c.decode_ms_quantised_batch(x, "i8", 8.0, 31, cap, bitsliced=True, **b, **kw),
-                             "bitsliced", (31, triple), False, note="bitsliced-" + note))
-            out.append(Entry("decode_ms_bitsliced_quantised_soft_batch", code, "q-i8", g,
-                             lambda c, x, cap, b, kw=kw: c.decode_ms_bitsliced_quantised_soft_batch(x, 8.0, 31, cap, **b, **kw),
-                             "bitsliced", (31, triple), True, app="i8", note=note))
-    # bit-sliced i8, two waves per group: the hard entries there are
-    for code in TWO_WAVES:
-        g = BS_GROUP[code]
-        out.append(Entry("decode_ms_batch", code, "i8", g, lambda c, x, cap, b: c.decode_ms_batch(x, cap, variant=BS, **b),
-                         "bitsliced", (127, None), False, note="bitsliced"))
-        out.append(Entry("decode_ms_corrected_fixed_batch", code, "i8", g,
-                         lambda c, x, cap, b: c.decode_ms_corrected_fixed_batch(x, *TRIPLE, cap, **b), "bitsliced", (127, TRIPLE), False))
-    return out
-
-
 ENTRIES = entries()
-
-
-def torch_dtype(kind):
-    import torch
-    return {"f32": torch.float32, "f64": torch.float64, "i8": torch.int8, "i16": torch.int16, "i32": torch.int32, "f16": torch.float16,
-            "bf16": torch.bfloat16, "q-i8": torch.float32, "q-i16": torch.float32}[kind]
-
-
-def host_rows(x, kind):
-    """pool rows as the CPU tensor that is copied into the device input (halves: the format's bits reinterpreted)"""
-    import torch
-    if kind in ("f16", "bf16"):
-        return torch.from_numpy(np.ascontiguousarray(x).view(np.int16)).view(torch_dtype(kind))
-    return torch.from_numpy(np.ascontiguousarray(x))
-
-
-def decoder_results(code, frames, soft, app_dtype):
-    import torch
-    res = []
-    if soft:
-        res.append(("app", torch.empty((frames, code.n() + code.punctured_bits()), dtype=app_dtype, device="cuda")))
-    return res + [("output", torch.empty((frames, code.output_len()), dtype=torch.uint8, device="cuda")),
-                  ("iters", torch.empty((frames,), dtype=torch.int32, device="cuda")),
-                  ("success", torch.empty((frames,), dtype=torch.uint8, device="cuda"))]
 
 
 def named(ref, idx, soft):
@@ -316,80 +85,6 @@ def test_entry_replays_on_other_frames(entry, cap):
 
 
 # ---- the streaming kernels ----------------------------------------------------------------------------------------------------------------
-def streaming_cases():
-    """id -> (code, build): build() returns (call, inputs, results, sets, refs) of captured.host_case"""
-    import torch
-    cases = {}
-
-    def put(name, code, build):
-        cases[f"{name}-{code.name}"] = (code, build)
-
-    def tensor(shape, dtype):
-        return torch.empty(shape, dtype=dtype, device="cuda")
-
-    def bf(code, cap):
-        words, _, _ = hard_frames.bf_pool(code)
-        res = hard_frames.bf_results(code, cap)
-        sets = [np.array([0, 16, 32, 1, 17]), np.array([33, 2, 18, 34, 3]), np.array([40, 41, 20, 21, 5])]
-        x = tensor((5, code.n() // 8), torch.uint8)
-        results = decoder_results(code, 5, False, None)
-        return (lambda: code.decode_bf_batch(x, cap, **dict(results)), [x], results, [[words[i]] for i in sets],
-                [{"output": res[0][i], "iters": res[1][i], "success": res[2][i]} for i in sets])
-
-    for cap in (0, 1, 20):
-        put(f"decode_bf_batch-cap{cap}", C.TM2048, functools.partial(bf, C.TM2048, cap))
-        put(f"decode_bf_batch-cap{cap}", C.TC256, functools.partial(bf, C.TC256, cap))
-
-    def encode(code):
-        data, cws = hard_frames.enc_pool(code)
-        sets = [np.arange(0, 5), np.arange(5, 10), np.arange(59, 64)]
-        x, y = tensor((5, code.k() // 8), torch.uint8), tensor((5, code.n() // 8), torch.uint8)
-        return (lambda: code.encode_batch(x, codewords=y), [x], [("codewords", y)], [[data[i]] for i in sets], [{"codewords": cws[i]} for i in sets])
-
-    for code in (C.TC256, C.TM2048, C.TM5120):
-        put("encode_batch", code, functools.partial(encode, code))
-
-    def hard_to_llrs(code, suf):
-        _, cws = hard_frames.enc_pool(code)
-        sets = [np.arange(0, 5), np.arange(11, 16)]
-        x, y = tensor((5, code.n() // 8), torch.uint8), tensor((5, code.n()), torch_dtype(suf))
-        want = [np.stack([oracle.hard_to_llrs(code, w, NP[suf]) for w in cws[i]]) for i in sets]
-        return (lambda: code.hard_to_llrs_batch(x, suf, llrs=y), [x], [("llrs", y)], [[cws[i]] for i in sets], [{"llrs": w} for w in want])
-
-    def llrs_to_hard(code, suf):
-        pool = small_pool(code, suf)[0]
-        sets = windows(len(pool), 5)
-        x, y = tensor((5, code.n()), torch_dtype(suf)), tensor((5, code.n() // 8), torch.uint8)
-        want = [np.stack([oracle.llrs_to_hard(code, r) for r in pool[i]]) for i in sets]
-        return (lambda: code.llrs_to_hard_batch(x, output=y), [x], [("hard", y)], [[pool[i]] for i in sets], [{"hard": w} for w in want])
-
-    for suf in ("f32", "f64", "i8", "i16", "i32"):
-        put(f"hard_to_llrs_batch-{suf}", C.TM1280, functools.partial(hard_to_llrs, C.TM1280, suf))
-        put(f"llrs_to_hard_batch-{suf}", C.TM1280, functools.partial(llrs_to_hard, C.TM1280, suf))
-
-    def quantise(code, suf):
-        pool = small_pool(code, "q-" + suf)[0]
-        sets = windows(len(pool), 5)
-        scale, lim = QUANT[suf]
-        x, y = tensor((5, code.n()), torch.float32), tensor((5, code.n()), torch_dtype(suf))
-        return (lambda: code.quantise_llrs_batch(x, suf, scale, lim, out=y), [x], [("quantised", y)], [[pool[i]] for i in sets],
-                [{"quantised": qr.quantise(pool[i], NP[suf], scale, lim)} for i in sets])
-
-    def widen_rows(code, fmt):
-        bits = small_pool(code, fmt)[0]
-        sets = windows(len(bits), 5)
-        x, y = tensor((5, code.n()), torch_dtype(fmt)), tensor((5, code.n()), torch.float32)
-        return (lambda: code.widen_llrs_batch(x, out=y), [x], [("widened", y)], [[host_rows(bits[i], fmt)] for i in sets],
-                [{"widened": widen(bits[i], fmt)} for i in sets])
-
-    for code in (C.TC256, C.TM6144):
-        for suf in ("i8", "i16"):
-            put(f"quantise_llrs_batch-{suf}", code, functools.partial(quantise, code, suf))
-        for fmt in ("f16", "bf16"):
-            put(f"widen_llrs_batch-{fmt}", code, functools.partial(widen_rows, code, fmt))
-    return cases
-
-
 STREAMING_IDS = (["decode_bf_batch-cap%d-%s" % (cap, c) for cap in (0, 1, 20) for c in ("TM2048", "TC256")]
                  + ["encode_batch-" + c for c in ("TC256", "TM2048", "TM5120")]
                  + ["%s-%s-TM1280" % (m, s) for s in ("f32", "f64", "i8", "i16", "i32") for m in ("hard_to_llrs_batch", "llrs_to_hard_batch")]
